@@ -9,7 +9,18 @@ One step = one full render of the batch (device plan -> generate -> spectral ->
 overlap-add -> FIR -> stereo/normalise) with the packed presets and IRs resident
 and the output left in HBM.  Weak scaling: every rank renders its own batch.
 
-    python bench.py [--gpus N --steps K --warmup W --config C3 --batch 1024 --points C4,C5]
+    python bench.py [--gpus N --steps K --warmup W --config C3 --batch 1024]
+    python bench.py --full [... --points C4,C5 --fir-points 16384,65536 --no-cpu]
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(metric, value, ms_per_step, the stage windows sampled inside those steps).
+``--full`` adds everything else the line has carried: the CPU baseline and the
+drop-in latency, the check against the reference's summaries, the roofline
+figures (timed and isolated), the steps timed again from param dicts, the
+secondary configs (``--points``) and the standalone FIR points
+(``--fir-points``).  ``--dump-outputs DIR`` writes what the last timed step
+rendered (dump_outputs below) so that two builds can be compared output for
+output: the presets and IRs are the same from run to run.
 
 Multi-GPU (presets are independent, no data-path
 collective), two launch modes with the same per-rank code:
@@ -476,6 +487,44 @@ class DryRunner:
         pass
 
 
+# --dump-outputs: at most DUMP_BYTES over a rank's sub-batches (the headline's
+# outputs are 3.1 GB per GPU), in blocks of DUMP_BLOCK consecutive frames
+DUMP_BYTES = 48 << 20
+DUMP_BLOCK = 4096
+DUMP_SEED = 384000
+
+
+def dump_rows(total, budget_rows, seed):
+    """Frames of a (total, 2) output buffer that --dump-outputs keeps: None (all
+    of them) when they fit budget_rows, else DUMP_BLOCK-frame blocks -- the first,
+    the last and a default_rng(seed) draw of the others -- in ascending order."""
+    if total <= budget_rows:
+        return None
+    nblk = -(-total // DUMP_BLOCK)
+    k = max(2, budget_rows // DUMP_BLOCK)
+    pick = np.random.default_rng(seed).choice(nblk - 2, size=k - 2, replace=False) + 1
+    blocks = np.sort(np.concatenate(([0], pick, [nblk - 1]))).astype(np.int64)
+    rows = (blocks[:, None] * DUMP_BLOCK + np.arange(DUMP_BLOCK, dtype=np.int64)).reshape(-1)
+    return rows[rows < total]
+
+
+def dump_outputs(runner, w, path, rank, world):
+    """Write the output buffers of the step just rendered, as its caller holds them
+    (one (frames, 2) float32 buffer per sub-batch, presets back to back), to
+    path/out_sub<i>.npy (rank<r>_out_sub<i>.npy when there are several ranks);
+    buffers above the budget are written as their dump_rows() frames."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    runner.sync()
+    budget_rows = DUMP_BYTES // (8 * len(w.outs))
+    for i, o in enumerate(w.outs):
+        rows = dump_rows(int(o.shape[0]), budget_rows, DUMP_SEED + i)
+        if rows is not None:
+            o = o.index_select(0, torch.from_numpy(rows).to(o.device))
+        name = f"out_sub{i}.npy" if world == 1 else f"rank{rank}_out_sub{i}.npy"
+        np.save(os.path.join(path, name), o.cpu().numpy().astype(np.float32, copy=False))
+
+
 def timed(runner, w, steps, warmup, comm, **kw):
     """W untimed steps, then K steps bracketed by barrier + device sync; returns
     (this rank's seconds, max over ranks)."""
@@ -492,8 +541,11 @@ def timed(runner, w, steps, warmup, comm, **kw):
     return mine, comm.max(mine)
 
 
-def measure(runner, cfg, seeds, sub, steps, warmup, comm, irs, golden, iso_steps=0, from_dicts_steps=0):
-    """Time one config on this rank; returns the point record (rank 0 fills it)."""
+def measure(runner, cfg, seeds, sub, steps, warmup, comm, irs, golden, iso_steps=0, from_dicts_steps=0,
+            full=True, dump=None):
+    """Time one config on this rank; returns the point record (rank 0 fills it).
+    full=False: the timed steps and their stage windows only; dump: the directory
+    the last timed step's outputs go to."""
     world = comm.world
     w = Workload(cfg, seeds, sub, irs, len(runner.engs))
     runner.prepare(w)
@@ -504,6 +556,15 @@ def measure(runner, cfg, seeds, sub, steps, warmup, comm, irs, golden, iso_steps
     mine, elapsed = timed(runner, w, steps, 0, comm)
     runner.profiling(False)
     stages = {n: round(float(v), 4) for n, v in zip(STAGE_NAMES, runner.stage_ms())}
+    if dump:
+        dump_outputs(runner, w, dump, comm.rank, world)
+    if not full:
+        rec = {"value": round(w.frames * world * steps / elapsed / 1e6, 3), "unit": "Msamples/s",
+               "ms_per_step": round(elapsed / steps * 1e3, 3), "steps": steps,
+               "workload": WORKLOAD.get(cfg, cfg), "presets_per_gpu": len(seeds), "sub_batches": len(w.subs),
+               "frames_per_gpu_step": w.frames, "stage_ms": stages, "_rank_s": mine}
+        runner.free(w)
+        return rec
     check = runner.check(w, golden) if comm.rank == 0 else None
     infos = runner.infos(w)
     nsub = len(w.subs)
@@ -743,6 +804,14 @@ def parse():
                     help="timed steps (100 C3 steps keep the GPU busy for ~1 s, long enough for an outside sampler)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the line can hold: CPU baseline, drop-in latency, "
+                         "check against the reference's summaries, rooflines (timed and isolated), steps from "
+                         "param dicts, the --points configs and the --fir-points filters.  Off: the options below "
+                         "that steer those parts have no effect")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the output buffers of the last timed step to DIR/out_sub<i>.npy (float32; buffers "
+                         "above the 48 MB budget as a fixed seeded sample of 4096-frame blocks)")
     ap.add_argument("--batch", type=int, default=0, help="presets per GPU (0: the config's default)")
     ap.add_argument("--sub", type=int, default=0, help="presets per in-flight sub-batch (0: config default)")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work")
@@ -844,25 +913,29 @@ def main():
     seeds = rank_seeds(rank, batch)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.dry_run:
         cpu = cpu_baseline(cfg, args.cpu_budget)
     comm = Comm(rank, world)
     try:
         if args.dry_run:
             return dry_main(args, comm, cfg, seeds, local, cpus, out)
         irs = load_irs()
-        with open(os.path.join(REPO, "tests", "golden", "golden_info.json")) as f:
-            golden = json.load(f)["summaries"]
-        with open(os.path.join(REPO, "tests", "golden", "golden_extra.json")) as f:
-            golden.update(json.load(f)["summaries"])          # H48_1000..1003 (tools/gen_golden_r3.py)
+        full = args.full
+        golden = {}
+        if full:
+            with open(os.path.join(REPO, "tests", "golden", "golden_info.json")) as f:
+                golden = json.load(f)["summaries"]
+            with open(os.path.join(REPO, "tests", "golden", "golden_extra.json")) as f:
+                golden.update(json.load(f)["summaries"])          # H48_1000..1003 (tools/gen_golden_r3.py)
         gate = None if args.gate in ("", "none") else tuple(int(v) for v in args.gate.split(","))
         head_gate = None if (cfg in GATE_OFF and args.gate == DEFAULT_GATE) else gate
         device = 0 if args.rehearse_one_gpu else local
         runner = GpuRunner(device, max(1, args.streams), head_gate, threaded=args.enqueue == "threads")
         head = measure(runner, cfg, seeds, default_sub(cfg, args, batch), args.steps, args.warmup, comm, irs,
-                       golden, iso_steps=args.iso_steps, from_dicts_steps=args.from_dicts_steps)
+                       golden, iso_steps=args.iso_steps, from_dicts_steps=args.from_dicts_steps,
+                       full=full, dump=args.dump_outputs)
         points = {}
-        for pc in [c for c in args.points.split(",") if c and c != cfg]:
+        for pc in [c for c in args.points.split(",") if full and c and c != cfg]:
             pb = default_batch(pc, args)
             # C5's 8 sub-batches of 128 ran 3 % slower gated (135.2 vs 139.5 ms per step)
             runner.set_gate(None if pc in GATE_OFF else gate)
@@ -872,10 +945,10 @@ def main():
                                  from_dicts_steps=psteps if (pc == "H48" and args.from_dicts_steps) else 0)
             if points[pc] is not None:
                 points[pc]["stream_gate"] = "none" if (pc in GATE_OFF or gate is None) else ",".join(map(str, gate))
-        for M in [int(t) for t in args.fir_points.split(",") if t]:
+        for M in [int(t) for t in args.fir_points.split(",") if full and t]:
             points[f"FIR{M // 1024}K"] = measure_fir(runner, M, max(args.point_steps, 20), comm, rank,
                                                      cpu=(rank == 0 and not args.no_cpu))
-        lat = dropin_latency(cpu) if (rank == 0 and world == 1 and not args.no_cpu) else None
+        lat = dropin_latency(cpu) if (full and rank == 0 and world == 1 and not args.no_cpu) else None
         ranks = comm.gather({"rank": rank, "pid": os.getpid(), "device": device,
                              "cpus": [cpus[0], cpus[-1], len(cpus)], "host_threads": host_threads(),
                              "seeds": [seeds[0], seeds[-1]], "elapsed_s": round(head["_rank_s"], 6),
@@ -887,32 +960,39 @@ def main():
                 "metric": "Msamples/sec rendered (microsound full pipe, 384 kHz->48 kHz) at 1/2/4/8 GPUs",
                 "value": head["value"], "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True,
-                "scaling": "weak", "vs_baseline": None, "dtype": "fp32",
+                "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "full": full,
                 "data": "synthetic presets (reference param dicts, seeds per rank), IRs from irs/",
                 "config": {"workload": head["workload"], "presets_per_gpu": batch,
                            "frames_per_gpu_step": head["frames_per_gpu_step"],
-                           "events_per_gpu_step": head["events_per_gpu_step"],
-                           "design_samples_per_gpu_step": head["design_samples_per_gpu_step"],
                            "sub_batches_per_gpu": head["sub_batches"],
                            "parallelism": f"preset-sharded x{world}" + (
                                " (rehearsal: every rank on device 0)" if args.rehearse_one_gpu else ""),
                            "streams_per_gpu": len(runner.engs),
                            "stream_gate": ",".join(map(str, head_gate)) if head_gate else "none", "enqueue": args.enqueue},
-                "roofline": head["roofline"], "roofline_isolated": head.get("roofline_isolated"),
-                "stage_ms": head["stage_ms"], "stage_algorithmic_GBs": head["stage_algorithmic_GBs"],
-                "design_msamples_per_s": head["design_msamples_per_s"],
+                "stage_ms": head["stage_ms"],
                 "stage_sampling": f"stage events on batches 0, {PROFILE_EVERY}, {2 * PROFILE_EVERY}, ... of each context",
-                "checked": head["check"],
-                "from_dicts": head.get("from_dicts"),
-                "cpu_baseline": cpu,
-                "dropin_latency": lat,
-                "points": points,
                 "ranks": ranks,
             }
+            if args.dump_outputs:
+                line["dumped_outputs"] = args.dump_outputs
+            if full:
+                line["config"].update({"events_per_gpu_step": head["events_per_gpu_step"],
+                                       "design_samples_per_gpu_step": head["design_samples_per_gpu_step"]})
+                line.update({
+                    "roofline": head["roofline"], "roofline_isolated": head.get("roofline_isolated"),
+                    "stage_algorithmic_GBs": head["stage_algorithmic_GBs"],
+                    "design_msamples_per_s": head["design_msamples_per_s"],
+                    "checked": head["check"],
+                    "from_dicts": head.get("from_dicts"),
+                    "cpu_baseline": cpu,
+                    "dropin_latency": lat,
+                    "points": points,
+                })
             if args.rehearse_one_gpu:
                 line["rehearsal"] = "all ranks shared device 0: checks the multi-rank path, not a scaling point"
-            # last, so that a reader keeping only the line's tail sees every point and its check
-            line["points_summary"] = points_summary(head, points)
+            if full:
+                # last, so that a reader keeping only the line's tail sees every point and its check
+                line["points_summary"] = points_summary(head, points)
             print(json.dumps(line), file=out, flush=True)
     finally:
         comm.close()

@@ -3,14 +3,14 @@
 # line when the suite ended normally (pass or test failures, no fault/timeout).
 set -o pipefail
 tag=${1:?usage: tools/gpu_round.sh TAG}
-mkdir -p gpurun_out
+O=${MSGPU_OUT:-bench_out}; mkdir -p "$O"
 timeout -k 10 500 python -u -m pytest tests -m gpu -v -s --timeout 200 --timeout-method thread \
-  > gpurun_out/${tag}_gpu_tests.txt 2>&1
+  > $O/${tag}_gpu_tests.txt 2>&1
 rc=$?
-echo "== suite rc=$rc"; grep -E "FAILED|passed|failed|Error" gpurun_out/${tag}_gpu_tests.txt | tail -12
+echo "== suite rc=$rc"; grep -E "FAILED|passed|failed|Error" $O/${tag}_gpu_tests.txt | tail -12
 if [ $rc -gt 1 ]; then exit $rc; fi
-timeout -k 10 600 python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.log || exit $?
-python3 - gpurun_out/${tag}_bench.json <<'PY'
+timeout -k 10 600 python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.log || exit $?
+python3 - $O/${tag}_bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 print("C3 step", d["ms_per_step"], "value", d["value"], "ok", d["checked"]["all_ok"], "roof", d["roofline"]["kernel"], d["roofline"]["frac"])

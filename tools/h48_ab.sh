@@ -9,7 +9,7 @@ grep -m1 'model name' /proc/cpuinfo
 for i in 1 2; do
  for lib in "$@"; do
   out=gpurun_out/${tag}_${lib%.so}_$i
-  MSGPU_LIB=audio-suite_amd/msgpu/$lib timeout -k 10 200 python bench.py --config H48 --no-cpu --points= --fir-points= \
+  MSGPU_LIB=audio-suite_amd/msgpu/$lib timeout -k 10 200 python bench.py --full --config H48 --no-cpu --points= --fir-points= \
     --steps 50 --from-dicts-steps 0 --iso-steps 1 > $out.json 2> $out.log || exit $?
   python3 -c "
 import json; d=json.load(open('$out.json')); s=d['stage_ms']

@@ -4,7 +4,7 @@ set -o pipefail
 R=$PWD; mkdir -p gpurun_out; export TMPDIR=/tmp
 tag=${1:-r06y}
 cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/${tag}_H48" -o run -- \
-  python3 "$R/bench.py" --config H48 --no-cpu --iso-steps 0 --points= --fir-points= --steps 20 --from-dicts-steps 0 \
+  python3 "$R/bench.py" --full --config H48 --no-cpu --iso-steps 0 --points= --fir-points= --steps 20 --from-dicts-steps 0 \
   > "$R/gpurun_out/${tag}_H48_bench.json" 2> "$R/gpurun_out/${tag}_H48.log" || exit $?
 cd "$R"
 python3 - "$tag" <<'PY'

@@ -13,7 +13,7 @@ bash tools/pmc_sq.sh "$tag" || exit $?
 for c in C4 C5; do
   steps=10; [ $c = C5 ] && steps=3
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/${tag}_$c" -o run -- \
-      python3 "$R/bench.py" --config $c --no-cpu --iso-steps 0 --points= --fir-points= --steps $steps \
+      python3 "$R/bench.py" --full --config $c --no-cpu --iso-steps 0 --points= --fir-points= --steps $steps \
       > "$R/gpurun_out/${tag}_${c}_bench.json" 2> "$R/gpurun_out/${tag}_$c.log") || exit $?
   python3 - "$tag" $c <<'PY'
 import csv, glob, json, sys

@@ -4,7 +4,7 @@
 #   usage (on the box): bash tools/round6_ab.sh NAME [args]
 # NAME: c3_streams c3_streams32 h48_host_diag h48_numa_diag h48_sched gate_points_ab gate_c3_ab h48_streams_ab prof_every_ab prof_every_ab2 h48_warmup_ab sub_sweep s3p_check fir8_cus_stamps ho_check q2nt_ab mb_check c5_sub_ab q2_ahead1_ab
 set -o pipefail
-mkdir -p gpurun_out
+O=${MSGPU_OUT:-bench_out}; mkdir -p "$O"
 
 # GPU box: the host share seen by the process (cgroup CPU quota, throttling
 # counters around each run) and H48 under several host pool sizes.
@@ -13,11 +13,11 @@ echo "cpu.max: $(cat /sys/fs/cgroup/cpu.max 2>/dev/null)"; echo "cpuset: $(cat /
 nproc
 for th in 16 8 16 4; do
   before=$(grep -E "nr_throttled|throttled_usec|usage_usec" /sys/fs/cgroup/cpu.stat 2>/dev/null | tr '\n' ' ')
-  MSGPU_HOST_THREADS=$th timeout -k 10 200 python bench.py --config H48 --no-cpu --points= --fir-points= \
-    --steps 50 --from-dicts-steps 0 --iso-steps 1 > gpurun_out/r06r_h48_t$th.json 2> gpurun_out/r06r_h48_t$th.log || exit $?
+  MSGPU_HOST_THREADS=$th timeout -k 10 200 python bench.py --full --config H48 --no-cpu --points= --fir-points= \
+    --steps 50 --from-dicts-steps 0 --iso-steps 1 > $O/r06r_h48_t$th.json 2> $O/r06r_h48_t$th.log || exit $?
   after=$(grep -E "nr_throttled|throttled_usec|usage_usec" /sys/fs/cgroup/cpu.stat 2>/dev/null | tr '\n' ' ')
   python3 -c "
-import json; d=json.load(open('gpurun_out/r06r_h48_t$th.json')); s=d['stage_ms']
+import json; d=json.load(open('$O/r06r_h48_t$th.json')); s=d['stage_ms']
 print('threads $th', d['ms_per_step'], {k: s.get(k) for k in ('host_prep','host_plan_wall','host_records_wall','host_upload_wall')})"
   echo "  before: $before"; echo "  after:  $after"
 done
@@ -37,10 +37,10 @@ PY
 lscpu | grep -E "NUMA|Socket|Thread|Core" || true
 run() {
   tag=$1; shift
-  timeout -k 10 200 "$@" python bench.py --config H48 --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
-    --iso-steps 1 > gpurun_out/r06s_$tag.json 2> gpurun_out/r06s_$tag.log || return $?
+  timeout -k 10 200 "$@" python bench.py --full --config H48 --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
+    --iso-steps 1 > $O/r06s_$tag.json 2> $O/r06s_$tag.log || return $?
   python3 -c "
-import json; d=json.load(open('gpurun_out/r06s_$tag.json')); s=d['stage_ms']
+import json; d=json.load(open('$O/r06s_$tag.json')); s=d['stage_ms']
 print('$tag', d['ms_per_step'], {k: s.get(k) for k in ('host_prep','host_plan_wall','host_records_wall','host_upload_wall')})"
 }
 read LOCAL REMOTE < <(python3 - <<'PY'
@@ -75,10 +75,10 @@ done
 h48_sched() {
 run() {
   tag=$1; shift
-  timeout -k 10 200 python bench.py --config H48 --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
-    --iso-steps 0 "$@" > gpurun_out/r06h48s_$tag.json 2> gpurun_out/r06h48s_$tag.log || return $?
+  timeout -k 10 200 python bench.py --full --config H48 --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
+    --iso-steps 0 "$@" > $O/r06h48s_$tag.json 2> $O/r06h48s_$tag.log || return $?
   python3 -c "
-import json; d=json.load(open('gpurun_out/r06h48s_$tag.json'))
+import json; d=json.load(open('$O/r06h48s_$tag.json'))
 print('$tag', '$*', d['ms_per_step'], d['checked']['all_ok'], d['config'].get('sub_batches_per_gpu'), d['config'].get('stream_gate'))"
 }
 for i in 1 2; do
@@ -96,10 +96,10 @@ done
 gate_points_ab() {
 run() {
   cfg=$1; tag=$2; shift 2
-  timeout -k 10 200 python bench.py --config $cfg --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
-    --iso-steps 0 "$@" > gpurun_out/r06g2_${cfg}_$tag.json 2> gpurun_out/r06g2_${cfg}_$tag.log || return $?
+  timeout -k 10 200 python bench.py --full --config $cfg --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
+    --iso-steps 0 "$@" > $O/r06g2_${cfg}_$tag.json 2> $O/r06g2_${cfg}_$tag.log || return $?
   python3 -c "
-import json; d=json.load(open('gpurun_out/r06g2_${cfg}_$tag.json'))
+import json; d=json.load(open('$O/r06g2_${cfg}_$tag.json'))
 print('$cfg $tag', d['ms_per_step'], d['checked']['all_ok'], d['config'].get('stream_gate'))"
 }
 for cfg in H48 C4; do
@@ -114,10 +114,10 @@ done
 gate_c3_ab() {
 for i in 1 2 3; do
   for g in 2,4 none; do
-    timeout -k 10 200 python bench.py --no-cpu --points= --fir-points= --steps 40 --from-dicts-steps 0 --iso-steps 0 \
-      --gate $g > gpurun_out/r06g3_${g/,/_}_$i.json 2> gpurun_out/r06g3_${g/,/_}_$i.log || exit $?
+    timeout -k 10 200 python bench.py --full --no-cpu --points= --fir-points= --steps 40 --from-dicts-steps 0 --iso-steps 0 \
+      --gate $g > $O/r06g3_${g/,/_}_$i.json 2> $O/r06g3_${g/,/_}_$i.log || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06g3_${g/,/_}_$i.json'))
+import json; d=json.load(open('$O/r06g3_${g/,/_}_$i.json'))
 print('C3 gate $g', $i, d['ms_per_step'], d['checked']['all_ok'])"
   done
 done
@@ -128,10 +128,10 @@ h48_streams_ab() {
 for i in 1 2; do
   for cfg in "3 341" "2 512" "4 256"; do
     set -- $cfg
-    timeout -k 10 200 python bench.py --config H48 --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
-      --iso-steps 0 --gate none --streams $1 --sub $2 > gpurun_out/r06hs_$1_$i.json 2> gpurun_out/r06hs_$1_$i.log || exit $?
+    timeout -k 10 200 python bench.py --full --config H48 --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
+      --iso-steps 0 --gate none --streams $1 --sub $2 > $O/r06hs_$1_$i.json 2> $O/r06hs_$1_$i.log || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06hs_$1_$i.json'))
+import json; d=json.load(open('$O/r06hs_$1_$i.json'))
 print('H48 streams $1 sub $2', $i, d['ms_per_step'], d['checked']['all_ok'])"
   done
 done
@@ -140,20 +140,20 @@ done
 # GPU box: sampled stage profiling (bench PROFILE_EVERY = 4) -- H48 and C3 lines,
 # and the stage-time GPU tests.
 prof_every_ab() {
-timeout -k 10 300 python -u -m pytest tests -m gpu -k "stage or profil or h48" -x -q --timeout 200 --timeout-method thread > gpurun_out/r06pe_tests.txt 2>&1
-rc=$?; echo "tests rc=$rc"; tail -2 gpurun_out/r06pe_tests.txt
+timeout -k 10 300 python -u -m pytest tests -m gpu -k "stage or profil or h48" -x -q --timeout 200 --timeout-method thread > $O/r06pe_tests.txt 2>&1
+rc=$?; echo "tests rc=$rc"; tail -2 $O/r06pe_tests.txt
 [ $rc -gt 1 ] && exit $rc
 for i in 1 2; do
-  timeout -k 10 200 python bench.py --config H48 --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
-    --iso-steps 0 > gpurun_out/r06pe_h48_$i.json 2> gpurun_out/r06pe_h48_$i.log || exit $?
+  timeout -k 10 200 python bench.py --full --config H48 --no-cpu --points= --fir-points= --steps 50 --from-dicts-steps 0 \
+    --iso-steps 0 > $O/r06pe_h48_$i.json 2> $O/r06pe_h48_$i.log || exit $?
   python3 -c "
-import json; d=json.load(open('gpurun_out/r06pe_h48_$i.json')); s=d['stage_ms']
+import json; d=json.load(open('$O/r06pe_h48_$i.json')); s=d['stage_ms']
 print('H48', d['ms_per_step'], d['checked']['all_ok'], d.get('stage_sampling'), {k: s[k] for k in ('generate','spectral','fir_kernel','stereo','total','host_plan_wall')})"
 done
-timeout -k 10 200 python bench.py --no-cpu --points= --fir-points= --steps 40 --from-dicts-steps 0 --iso-steps 0 \
-  > gpurun_out/r06pe_c3.json 2> gpurun_out/r06pe_c3.log || exit $?
+timeout -k 10 200 python bench.py --full --no-cpu --points= --fir-points= --steps 40 --from-dicts-steps 0 --iso-steps 0 \
+  > $O/r06pe_c3.json 2> $O/r06pe_c3.log || exit $?
 python3 -c "
-import json; d=json.load(open('gpurun_out/r06pe_c3.json')); s=d['stage_ms']
+import json; d=json.load(open('$O/r06pe_c3.json')); s=d['stage_ms']
 print('C3', d['ms_per_step'], d['checked']['all_ok'], d['roofline']['frac'], {k: s[k] for k in ('generate','spectral','overlap_add','fir_kernel','stereo','total')})"
 }
 
@@ -162,10 +162,10 @@ print('C3', d['ms_per_step'], d['checked']['all_ok'], d['roofline']['frac'], {k:
 prof_every_ab2() {
 for i in 1 2; do
   for k in 1 4 16 0; do
-    MSGPU_BENCH_PROFILE_EVERY=$k timeout -k 10 200 python bench.py --config H48 --no-cpu --points= --fir-points= \
-      --steps 50 --from-dicts-steps 0 --iso-steps 0 > gpurun_out/r06pe2_${k}_$i.json 2> gpurun_out/r06pe2_${k}_$i.log || exit $?
+    MSGPU_BENCH_PROFILE_EVERY=$k timeout -k 10 200 python bench.py --full --config H48 --no-cpu --points= --fir-points= \
+      --steps 50 --from-dicts-steps 0 --iso-steps 0 > $O/r06pe2_${k}_$i.json 2> $O/r06pe2_${k}_$i.log || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06pe2_${k}_$i.json'))
+import json; d=json.load(open('$O/r06pe2_${k}_$i.json'))
 print('H48 every $k', $i, d['ms_per_step'], d['checked']['all_ok'])"
   done
 done
@@ -176,10 +176,10 @@ h48_warmup_ab() {
 for i in 1 2; do
   for cfg in "3 1" "30 1" "3 0" "30 0"; do
     set -- $cfg
-    MSGPU_BENCH_PROFILE_EVERY=$2 timeout -k 10 200 python bench.py --config H48 --no-cpu --points= --fir-points= \
-      --steps 50 --warmup $1 --from-dicts-steps 0 --iso-steps 0 > gpurun_out/r06wu_$1_$2_$i.json 2> gpurun_out/r06wu_$1_$2_$i.log || exit $?
+    MSGPU_BENCH_PROFILE_EVERY=$2 timeout -k 10 200 python bench.py --full --config H48 --no-cpu --points= --fir-points= \
+      --steps 50 --warmup $1 --from-dicts-steps 0 --iso-steps 0 > $O/r06wu_$1_$2_$i.json 2> $O/r06wu_$1_$2_$i.log || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06wu_$1_$2_$i.json'))
+import json; d=json.load(open('$O/r06wu_$1_$2_$i.json'))
 print('H48 warmup $1 every $2', $i, d['ms_per_step'], d['checked']['all_ok'])"
   done
 done
@@ -189,10 +189,10 @@ done
 sub_sweep() {
 run() {
   cfg=$1; sub=$2; i=$3
-  timeout -k 10 200 python bench.py --config $cfg --no-cpu --points= --fir-points= --steps 30 --from-dicts-steps 0 \
-    --iso-steps 0 --sub $sub > gpurun_out/r06ss_${cfg}_${sub}_$i.json 2> gpurun_out/r06ss_${cfg}_${sub}_$i.log || return $?
+  timeout -k 10 200 python bench.py --full --config $cfg --no-cpu --points= --fir-points= --steps 30 --from-dicts-steps 0 \
+    --iso-steps 0 --sub $sub > $O/r06ss_${cfg}_${sub}_$i.json 2> $O/r06ss_${cfg}_${sub}_$i.log || return $?
   python3 -c "
-import json; d=json.load(open('gpurun_out/r06ss_${cfg}_${sub}_$i.json'))
+import json; d=json.load(open('$O/r06ss_${cfg}_${sub}_$i.json'))
 print('$cfg sub $sub', $i, d['ms_per_step'], d['checked']['all_ok'], d['config'].get('sub_batches_per_gpu'))"
 }
 for i in 1 2; do
@@ -206,11 +206,11 @@ done
 # then the isolated / timed A/B on C3 and C4.
 s3p_check() {
 L=audio-suite_amd/msgpu/libmsgpu.so
-timeout -k 10 300 python tools/bits_ab.py "$L,MSGPU_SPEC3P=0" "$L,MSGPU_SPEC3P=1" > gpurun_out/r06u_bits.json 2> gpurun_out/r06u_bits.log
-echo "bits rc=$?"; cat gpurun_out/r06u_bits.json
-timeout -k 10 400 python -u -m pytest tests/test_gpu_long_filters.py -k 'spec3_persistent or fir8_persistent' -m gpu -x -q -s --timeout 200 --timeout-method thread > gpurun_out/r06u_tests0.txt 2>&1; echo "persist test rc=$?"; tail -3 gpurun_out/r06u_tests0.txt
-MSGPU_SPEC3P=1 timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -k 'spec3 or C3 or C4' -m gpu -x -q --timeout 200 --timeout-method thread > gpurun_out/r06u_tests.txt 2>&1
-rc=$?; echo "tests rc=$rc"; tail -3 gpurun_out/r06u_tests.txt
+timeout -k 10 300 python tools/bits_ab.py "$L,MSGPU_SPEC3P=0" "$L,MSGPU_SPEC3P=1" > $O/r06u_bits.json 2> $O/r06u_bits.log
+echo "bits rc=$?"; cat $O/r06u_bits.json
+timeout -k 10 400 python -u -m pytest tests/test_gpu_long_filters.py -k 'spec3_persistent or fir8_persistent' -m gpu -x -q -s --timeout 200 --timeout-method thread > $O/r06u_tests0.txt 2>&1; echo "persist test rc=$?"; tail -3 $O/r06u_tests0.txt
+MSGPU_SPEC3P=1 timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -k 'spec3 or C3 or C4' -m gpu -x -q --timeout 200 --timeout-method thread > $O/r06u_tests.txt 2>&1
+rc=$?; echo "tests rc=$rc"; tail -3 $O/r06u_tests.txt
 [ $rc -gt 1 ] && exit $rc
 bash tools/ab_env.sh r06u 'p0|MSGPU_SPEC3P=0|base' 'p1|MSGPU_SPEC3P=1|base' 'p0b|MSGPU_SPEC3P=0|base' 'p1b|MSGPU_SPEC3P=1|base'
 }
@@ -230,10 +230,10 @@ c3_streams() {
 for i in 1 2; do
   for cfg in "3 342" "2 512" "4 256"; do
     set -- $cfg
-    timeout -k 10 200 python bench.py --no-cpu --points= --fir-points= --steps 30 --from-dicts-steps 0 --iso-steps 0 \
-      --streams $1 --sub $2 > gpurun_out/r06c3s_$1_$i.json 2> gpurun_out/r06c3s_$1_$i.log || exit $?
+    timeout -k 10 200 python bench.py --full --no-cpu --points= --fir-points= --steps 30 --from-dicts-steps 0 --iso-steps 0 \
+      --streams $1 --sub $2 > $O/r06c3s_$1_$i.json 2> $O/r06c3s_$1_$i.log || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06c3s_$1_$i.json'))
+import json; d=json.load(open('$O/r06c3s_$1_$i.json'))
 print('C3 streams $1 sub $2', $i, d['ms_per_step'], d['checked']['all_ok'])"
   done
 done
@@ -244,10 +244,10 @@ c3_streams32() {
 for i in 1 2 3 4; do
   for cfg in "3 342" "2 512"; do
     set -- $cfg
-    timeout -k 10 200 python bench.py --no-cpu --points= --fir-points= --steps 40 --from-dicts-steps 0 --iso-steps 0 \
-      --streams $1 --sub $2 > gpurun_out/r06c32_$1_$i.json 2> gpurun_out/r06c32_$1_$i.log || exit $?
+    timeout -k 10 200 python bench.py --full --no-cpu --points= --fir-points= --steps 40 --from-dicts-steps 0 --iso-steps 0 \
+      --streams $1 --sub $2 > $O/r06c32_$1_$i.json 2> $O/r06c32_$1_$i.log || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06c32_$1_$i.json'))
+import json; d=json.load(open('$O/r06c32_$1_$i.json'))
 print('C3 streams $1 sub $2', $i, d['ms_per_step'], d['checked']['all_ok'])"
   done
 done
@@ -255,15 +255,15 @@ done
 
 # FIR8 spectra with Ho at a 128-byte-aligned offset vs the HEAD library (libmsgpu_head.so): bits, FIR tests, C3 and FIR-point A/B
 ho_check() {
-timeout -k 10 300 python tools/bits_ab.py audio-suite_amd/msgpu/libmsgpu_head.so > gpurun_out/r06ho_bits.json 2>/dev/null; echo "bits rc=$?"; cat gpurun_out/r06ho_bits.json
-timeout -k 10 400 python -u -m pytest tests/test_gpu_fir.py tests/test_gpu_long_filters.py -m gpu -x -q --timeout 200 --timeout-method thread > gpurun_out/r06ho_tests.txt 2>&1; rc=$?; echo "tests rc=$rc"; tail -2 gpurun_out/r06ho_tests.txt
+timeout -k 10 300 python tools/bits_ab.py audio-suite_amd/msgpu/libmsgpu_head.so > $O/r06ho_bits.json 2>/dev/null; echo "bits rc=$?"; cat $O/r06ho_bits.json
+timeout -k 10 400 python -u -m pytest tests/test_gpu_fir.py tests/test_gpu_long_filters.py -m gpu -x -q --timeout 200 --timeout-method thread > $O/r06ho_tests.txt 2>&1; rc=$?; echo "tests rc=$rc"; tail -2 $O/r06ho_tests.txt
 [ $rc -gt 1 ] && exit $rc
 bash tools/ab_env.sh r06ho "new|MSGPU_X=1|base" "old|MSGPU_X=1|head" "new2|MSGPU_X=1|base" "old2|MSGPU_X=1|head"
 for lib in base head; do
   if [ $lib = base ]; then le=""; else le="MSGPU_LIB=$PWD/audio-suite_amd/msgpu/libmsgpu_head.so"; fi
-  env $le timeout -k 10 300 python bench.py --no-cpu --points= --steps 5 --from-dicts-steps 0 --iso-steps 0 > gpurun_out/r06ho_fir_$lib.json 2>/dev/null || exit $?
+  env $le timeout -k 10 300 python bench.py --full --no-cpu --points= --steps 5 --from-dicts-steps 0 --iso-steps 0 > $O/r06ho_fir_$lib.json 2>/dev/null || exit $?
   python3 -c "
-import json; d=json.load(open('gpurun_out/r06ho_fir_$lib.json')); print('$lib', {k: (v['ms_per_step'], v['roofline']['frac'], v['check']['all_ok']) for k, v in d['points'].items()})"
+import json; d=json.load(open('$O/r06ho_fir_$lib.json')); print('$lib', {k: (v['ms_per_step'], v['roofline']['frac'], v['check']['all_ok']) for k, v in d['points'].items()})"
 done
 }
 
@@ -273,19 +273,19 @@ L=$PWD/audio-suite_amd/msgpu
 for rep in 1 2 3; do
   for lib in base nt1 nt3; do
     if [ $lib = base ]; then le=""; else le="MSGPU_LIB=$L/libmsgpu_$lib.so"; fi
-    env $le timeout -k 10 300 python bench.py --no-cpu --points= --steps 5 --from-dicts-steps 0 --iso-steps 0 > gpurun_out/r06nt_$lib$rep.json 2>/dev/null || exit $?
+    env $le timeout -k 10 300 python bench.py --full --no-cpu --points= --steps 5 --from-dicts-steps 0 --iso-steps 0 > $O/r06nt_$lib$rep.json 2>/dev/null || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06nt_$lib$rep.json')); print('$lib$rep', {k: (v['ms_per_step'], v['roofline']['frac'], v['check']['all_ok']) for k, v in d['points'].items() if k.startswith('FIR')})"
+import json; d=json.load(open('$O/r06nt_$lib$rep.json')); print('$lib$rep', {k: (v['ms_per_step'], v['roofline']['frac'], v['check']['all_ok']) for k, v in d['points'].items() if k.startswith('FIR')})"
   done
 done
 }
 
 # maxbits zeroed through the batch upload (no fill launch): bits, stereo / peak tests, H48 and C3 A/B vs HEAD lib
 mb_check() {
-timeout -k 10 300 python tools/bits_ab.py audio-suite_amd/msgpu/libmsgpu_head.so > gpurun_out/r06mb_bits.json 2>/dev/null || exit $?
-python3 -c "import json; d=json.load(open('gpurun_out/r06mb_bits.json')); print('identical', d['identical'], d['differing_presets'])"
-timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > gpurun_out/r06mb_tests.txt 2>&1; rc=$?
-echo "tests rc=$rc"; tail -2 gpurun_out/r06mb_tests.txt
+timeout -k 10 300 python tools/bits_ab.py audio-suite_amd/msgpu/libmsgpu_head.so > $O/r06mb_bits.json 2>/dev/null || exit $?
+python3 -c "import json; d=json.load(open('$O/r06mb_bits.json')); print('identical', d['identical'], d['differing_presets'])"
+timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/r06mb_tests.txt 2>&1; rc=$?
+echo "tests rc=$rc"; tail -2 $O/r06mb_tests.txt
 [ $rc -ne 0 ] && exit $rc
 bash tools/h48_ab.sh r06mb libmsgpu.so libmsgpu_head.so || exit $?
 bash tools/ab_env.sh r06mb "new|MSGPU_X=1|base" "old|MSGPU_X=1|head" "new2|MSGPU_X=1|base" "old2|MSGPU_X=1|head"
@@ -295,10 +295,10 @@ bash tools/ab_env.sh r06mb "new|MSGPU_X=1|base" "old|MSGPU_X=1|head" "new2|MSGPU
 c5_sub_ab() {
 for i in ${C5_REPS:-1 2}; do
   for sub in ${C5_SUBS:-171 114}; do
-    timeout -k 10 300 python bench.py --config C5 --no-cpu --points= --fir-points= --steps 3 --warmup 1 --iso-steps 0 \
-      --from-dicts-steps 0 --sub $sub > gpurun_out/r06c5s_${sub}_$i.json 2> gpurun_out/r06c5s_${sub}_$i.log || exit $?
+    timeout -k 10 300 python bench.py --full --config C5 --no-cpu --points= --fir-points= --steps 3 --warmup 1 --iso-steps 0 \
+      --from-dicts-steps 0 --sub $sub > $O/r06c5s_${sub}_$i.json 2> $O/r06c5s_${sub}_$i.log || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06c5s_${sub}_$i.json'))
+import json; d=json.load(open('$O/r06c5s_${sub}_$i.json'))
 print('C5 sub $sub', $i, d['ms_per_step'], d['checked']['all_ok'], d['config'].get('sub_batches_per_gpu'), d['config'].get('stream_gate'))"
   done
 done
@@ -310,9 +310,9 @@ L=$PWD/audio-suite_amd/msgpu
 for rep in 1 2 3; do
   for lib in base a1; do
     if [ $lib = base ]; then le=""; else le="MSGPU_LIB=$L/libmsgpu_$lib.so"; fi
-    env $le timeout -k 10 300 python bench.py --no-cpu --points= --steps 5 --from-dicts-steps 0 --iso-steps 0 > gpurun_out/r06a1_$lib$rep.json 2>/dev/null || exit $?
+    env $le timeout -k 10 300 python bench.py --full --no-cpu --points= --steps 5 --from-dicts-steps 0 --iso-steps 0 > $O/r06a1_$lib$rep.json 2>/dev/null || exit $?
     python3 -c "
-import json; d=json.load(open('gpurun_out/r06a1_$lib$rep.json')); print('$lib$rep', {k: (v['ms_per_step'], v['roofline']['frac'], v['check']['all_ok']) for k, v in d['points'].items() if k.startswith('FIR')})"
+import json; d=json.load(open('$O/r06a1_$lib$rep.json')); print('$lib$rep', {k: (v['ms_per_step'], v['roofline']['frac'], v['check']['all_ok']) for k, v in d['points'].items() if k.startswith('FIR')})"
   done
 done
 }

@@ -6,7 +6,7 @@
 # alternating C4 and C3 bench runs.
 set -o pipefail
 tag=$1; old=$2; new=$3
-mkdir -p gpurun_out
+O=${MSGPU_OUT:-bench_out}; mkdir -p "$O"
 L=$PWD/audio-suite_amd/msgpu
 lib() { if [ "$1" = base ]; then echo ""; else echo "$L/libmsgpu_$1.so"; fi; }
 for c in C3 C4; do
@@ -20,20 +20,20 @@ print('$c bit-identical', np.array_equal(a,b), 'max abs diff', float(np.abs(a-b)
 done
 rm -f /tmp/${tag}_*.npy
 MSGPU_LIB=$(lib $new) timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_long_filters.py -m gpu -x -q \
-  --timeout 200 --timeout-method thread > gpurun_out/${tag}_tests.txt 2>&1 || { tail -20 gpurun_out/${tag}_tests.txt; exit 1; }
-tail -1 gpurun_out/${tag}_tests.txt
+  --timeout 200 --timeout-method thread > $O/${tag}_tests.txt 2>&1 || { tail -20 $O/${tag}_tests.txt; exit 1; }
+tail -1 $O/${tag}_tests.txt
 for v in $old $new; do
   if [ -f $L/libmsgpu_st$v.so ]; then
     for c in C3 C4; do
-      MSGPU_LIB=$L/libmsgpu_st$v.so timeout -k 10 200 python tools/spec3_stamps.py $c 171 > gpurun_out/${tag}_st_${v}_$c.txt 2>&1 || exit $?
-      echo "== stamps $v $c"; grep -v amdgpu.ids gpurun_out/${tag}_st_${v}_$c.txt
+      MSGPU_LIB=$L/libmsgpu_st$v.so timeout -k 10 200 python tools/spec3_stamps.py $c 171 > $O/${tag}_st_${v}_$c.txt 2>&1 || exit $?
+      echo "== stamps $v $c"; grep -v amdgpu.ids $O/${tag}_st_${v}_$c.txt
     done
   fi
 done
 run() {  # tag lib args...
   local t=$1 v=$2; shift 2
-  MSGPU_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --no-cpu --from-dicts-steps 0 --points= "$@" > gpurun_out/${tag}_$t.json 2> gpurun_out/${tag}_$t.log || exit $?
-  python3 - gpurun_out/${tag}_$t.json $t <<'PY'
+  MSGPU_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --full --no-cpu --from-dicts-steps 0 --points= "$@" > $O/${tag}_$t.json 2> $O/${tag}_$t.log || exit $?
+  python3 - $O/${tag}_$t.json $t <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 i = (d.get("roofline_isolated") or {}).get("stage_ms") or {}
