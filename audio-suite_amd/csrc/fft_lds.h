@@ -63,14 +63,10 @@ MSG_DEV float2 ff(f2v a) { return make_float2(a.x, a.y); }
 // broadcast into neg_lo/op_sel (k_fir2: 451 v_xor + 836 v_mov of 4952 VALU).
 // Products with compile-time constants (twc) keep the vector form, whose
 // constants the compiler places in SGPRs.
-#ifndef MSG_ASM_CMUL
-#define MSG_ASM_CMUL 1
-#endif
 MSG_DEV float2 cmul_v(float2 a, float2 b) {
     return ff(f2v{a.x, a.x} * f2v{b.x, b.y} + f2v{-a.y, a.y} * f2v{b.y, b.x});
 }
 MSG_DEV float2 cmul(float2 a, float2 b) {
-#if MSG_ASM_CMUL
     const f2v x = vv(a), y = vv(b);
     f2v r, t;
     // t = (a.x b.x, a.x b.y);  r = (-a.y b.y + t.x, a.y b.x + t.y)
@@ -78,79 +74,51 @@ MSG_DEV float2 cmul(float2 a, float2 b) {
         "v_pk_fma_f32 %0, %2, %3, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"
         : "=v"(r), "=&v"(t) : "v"(x), "v"(y));
     return ff(r);
-#else
-    return cmul_v(a, b);
-#endif
 }
 // a * b for a wave-uniform (compile-time) b, held in an SGPR pair
 MSG_DEV float2 cmul_k(float2 a, float2 b) {
-#if MSG_ASM_CMUL
     const f2v x = vv(a), y = vv(b);
     f2v r, t;
     asm("v_pk_mul_f32 %1, %2, %3 op_sel_hi:[0,1]\n\t"
         "v_pk_fma_f32 %0, %2, %3, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"
         : "=v"(r), "=&v"(t) : "v"(x), "s"(y));
     return ff(r);
-#else
-    return cmul_v(a, b);
-#endif
 }
 // a + (-+i) d and a - (-+i) d (forward sign -1, inverse +1) as single packed adds
 template <bool INV> MSG_DEV f2v add_mi(f2v a, f2v d) {
-#if MSG_ASM_CMUL
     f2v r;
     if (INV) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(d));
     else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(d));
     return r;
-#else
-    return a + f2v{d.y, d.x} * (INV ? f2v{-1.f, 1.f} : f2v{1.f, -1.f});
-#endif
 }
 template <bool INV> MSG_DEV f2v sub_mi(f2v a, f2v d) { return add_mi<!INV>(a, d); }
 // acc + (b.y, b.x) * (s, -s): the odd-radix sine term, s wave-uniform
 MSG_DEV f2v fma_swap_k(f2v b, f2v sv, f2v acc) {
-#if MSG_ASM_CMUL
     f2v r;
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1]" : "=v"(r) : "v"(b), "s"(sv), "v"(acc));
     return r;
-#else
-    return acc + f2v{b.y, b.x} * sv;
-#endif
 }
 // acc + a * b (complex multiply-accumulate in two packed FMAs)
 MSG_DEV float2 cfma(float2 acc, float2 a, float2 b) {
-#if MSG_ASM_CMUL
     const f2v x = vv(a), y = vv(b), c = vv(acc);
     f2v r, t;
     asm("v_pk_fma_f32 %1, %2, %3, %4 op_sel_hi:[0,1,1]\n\t"
         "v_pk_fma_f32 %0, %2, %3, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"
         : "=v"(r), "=&v"(t) : "v"(x), "v"(y), "v"(c));
     return ff(r);
-#else
-    return ff(vv(acc) + vv(cmul_v(a, b)));
-#endif
 }
 // (a.x + b.x, a.y - b.y) and (a.x - b.x, a.y + b.y): a + conj(b), a - conj(b)
 MSG_DEV f2v add_conj(f2v a, f2v b) {
-#if MSG_ASM_CMUL
     f2v r;
     asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return f2v{a.x + b.x, a.y - b.y};
-#endif
 }
 MSG_DEV f2v sub_conj(f2v a, f2v b) {
-#if MSG_ASM_CMUL
     f2v r;
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return f2v{a.x - b.x, a.y + b.y};
-#endif
 }
 MSG_DEV float2 cmulc(float2 a, float2 b) {   // a * conj(b)
-#if MSG_ASM_CMUL
     const f2v x = vv(a), y = vv(b);
     f2v r, t;
     // t = (a.x b.x, a.y b.x);  r = (a.y b.y + t.x, -a.x b.y + t.y)
@@ -158,9 +126,6 @@ MSG_DEV float2 cmulc(float2 a, float2 b) {   // a * conj(b)
         "v_pk_fma_f32 %0, %2, %3, %1 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
         : "=v"(r), "=&v"(t) : "v"(x), "v"(y));
     return ff(r);
-#else
-    return ff(f2v{a.x, a.y} * f2v{b.x, b.x} + f2v{a.y, -a.x} * f2v{b.y, b.y});
-#endif
 }
 MSG_DEV float2 cadd(float2 a, float2 b) { return ff(vv(a) + vv(b)); }
 MSG_DEV float2 csub(float2 a, float2 b) { return ff(vv(a) - vv(b)); }
@@ -426,14 +391,10 @@ MSG_DEV void stockham_fwd(float2* buf, int size, const int32_t* rad, int nrad, c
 // kernel's data loads even issue (k_fir8: 4 iterations, k_spec3: 2).  Kernels
 // issue their data loads between fetch() and put(); put() then waits for the
 // table loads only (vmcnt counts in order), and the data loads' latency runs
-// under the stores and the barrier.  MSG_TAB_PRELOAD=0 (tuning A/B): the loop.
-#ifndef MSG_TAB_PRELOAD
-#define MSG_TAB_PRELOAD 1
-#endif
+// under the stores and the barrier.
 template <int N, int T>
 struct TabCopy {
     static constexpr int PER = (N + T - 1) / T;
-#if MSG_TAB_PRELOAD
     float2 v[PER];
     MSG_DEV void fetch(const float2* __restrict__ src) {
 #pragma unroll
@@ -449,13 +410,6 @@ struct TabCopy {
             if (i < PER - 1 || k < N) dst[k] = v[i];
         }
     }
-#else
-    const float2* s = nullptr;
-    MSG_DEV void fetch(const float2* __restrict__ src) { s = src; }
-    MSG_DEV void put(float2* dst) const {
-        for (int k = threadIdx.x; k < N; k += T) dst[k] = s[k];
-    }
-#endif
 };
 
 // Copy the plan's twiddle tables into LDS at `dst` (after the data region).

@@ -451,7 +451,7 @@ template <bool OLA>
 __global__ void __launch_bounds__(fir8::T)
 k_fir8p(const PresetRt* __restrict__ rt, const int2* __restrict__ jobs, int n_jobs, const float2* __restrict__ tables,
         const float2* __restrict__ hspec, const float* __restrict__ x_in, float* __restrict__ y_out,
-        int32_t* __restrict__ ctr, int stagger, const msg_event* __restrict__ events,
+        int32_t* __restrict__ ctr, const msg_event* __restrict__ events,
         const float* __restrict__ grain_pool, const int32_t* __restrict__ ev_lo) {
     using namespace fir8;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
@@ -460,14 +460,6 @@ k_fir8p(const PresetRt* __restrict__ rt, const int2* __restrict__ jobs, int n_jo
     float2* buf = lds + G::TAB;
     const int t = otid();
     { TabCopy<G::TAB_USED, T> tc; tc.fetch(tables); tc.put(tab); }
-    // Stagger (MSGPU_FIR8P_STAGGER wall-clock ticks of 10 ns): every other
-    // workgroup of an XCD starts its first block that much later, so the two
-    // halves of the chip load their 256 KB segments and store their outputs
-    // out of phase instead of all together.
-    if (stagger > 0 && ((blockIdx.x / MSG_XCDS) & 1)) {
-        const long long t_end = wall_clock64() + stagger;
-        while (wall_clock64() < t_end) __builtin_amdgcn_s_sleep(16);
-    }
     // ctr[x * FIR8P_CTR]: XCD x's next block; ctr[MSG_XCDS * FIR8P_CTR]: workgroups
     // done.  The last workgroup to finish zeroes them for the next launch (no
     // memset kernel: one would queue for a CU behind the other streams' work).
@@ -592,28 +584,19 @@ MSG_DEV void q2_pair(float2 xk, float2 xm, float2 h0k, float2 h0m, float2 h1k, f
     }
 }
 // this thread's carries of pair r of one half (elements r and R4 + r at e T + t),
-// loaded MSG_Q2_AHEAD pairs ahead of their use; the empty asm statements (memory
-// clobbers) keep the compiler from hoisting every load to the top of the half
-// (sixteen carries beside v, b and the accumulators: scratch spills).  Measured
-// at 64 k taps per 1024 x 384 000 (profiles/r06h_fir8q_prefetch_ab.txt): 0 pairs
-// ahead 2.89 / 2.90 ms, 2 ahead 2.96 / 2.94, 4 ahead 3.14 / 3.10 (each pair
-// ahead costs 16 B of scratch spills per lane); 1 ahead 2.92 vs 2.88 – 2.90
-// (profiles/r06a1_fir8q_ahead1_ab.txt)
-#ifndef MSG_Q2_AHEAD
-#define MSG_Q2_AHEAD 0
-#endif
-constexpr int Q2_AHEAD = MSG_Q2_AHEAD;
+// loaded right before their use; the empty asm statements (memory clobbers) keep
+// the compiler from hoisting every load to the top of the half (sixteen carries
+// beside v, b and the accumulators: scratch spills).  Loading them pairs ahead
+// measured slower at 64 k taps per 1024 x 384 000
+// (profiles/r06h_fir8q_prefetch_ab.txt): 0 pairs ahead 2.89 / 2.90 ms, 2 ahead
+// 2.96 / 2.94, 4 ahead 3.14 / 3.10 (each pair ahead costs 16 B of scratch spills
+// per lane); 1 ahead 2.92 vs 2.88 – 2.90 (profiles/r06a1_fir8q_ahead1_ab.txt)
 MSG_DEV void q2_carry_load(const float2* sl, bool prev, int r, float2 (&c)[2][R4]) {
-    if (r >= R4) return;
     const uint32_t tu = (uint32_t)otid();
     asm volatile("" ::: "memory");
     c[0][r] = prev ? at32(sl, tu + (uint32_t)(r * T)) : make_float2(0.f, 0.f);
     c[1][r] = prev ? at32(sl, tu + (uint32_t)((R4 + r) * T)) : make_float2(0.f, 0.f);
     asm volatile("" ::: "memory");
-}
-MSG_DEV void q2_carry_first(const float2* sl, bool prev, float2 (&c)[2][R4]) {
-#pragma unroll
-    for (int r = 0; r < Q2_AHEAD; ++r) q2_carry_load(sl, prev, r, c);
 }
 
 // Even half of a block on the carry form (k_fir8's even_mac_pre with H0, plus
@@ -623,7 +606,6 @@ MSG_DEV void even_q2(const float2* tab, const float2 (&v)[2][R4], const float2* 
     const int t = otid();
     const uint32_t tu = (uint32_t)t;
     float2 c[2][R4];
-    q2_carry_first(sl, prev, c);
     if (t != 0) {
         const float2 wA = fir4_wM(tab, G::OFF_PLO, G::OFF_PHI, t);
 #pragma unroll
@@ -631,7 +613,7 @@ MSG_DEV void even_q2(const float2* tab, const float2 (&v)[2][R4], const float2* 
             const int kA = t + r * NB4;
             const float2 wk = cmul_k(wA, fir_cr<R4>(r));
             float2 xk, xm;
-            q2_carry_load(sl, prev, r + Q2_AHEAD, c);
+            q2_carry_load(sl, prev, r, c);
             fir_split(v[0][r], v[1][R4 - 1 - r], wk, xk, xm);
             q2_pair(xk, xm, at32(H0, kA), at32(H0, MH - kA), at32(H1, kA), at32(H1, MH - kA), acc[0][r],
                     acc[1][R4 - 1 - r], c[0][r], c[1][r], at32(sl, tu + (uint32_t)(r * T)),
@@ -644,7 +626,7 @@ MSG_DEV void even_q2(const float2* tab, const float2 (&v)[2][R4], const float2* 
 #pragma unroll
         for (int r = 0; r < R4; ++r) {
             const int kA = fir_k0<MH, R4>(r);
-            q2_carry_load(sl, prev, r + Q2_AHEAD, c);
+            q2_carry_load(sl, prev, r, c);
             if (r < R4 - 1) {
                 float2 xk, xm;
                 fir_split(a[r], bb[R4 - 1 - r], fir_w0<MH, R4>(r), xk, xm);
@@ -682,14 +664,13 @@ MSG_DEV void odd_q2(const float2* tab, const float2 (&v)[2][R4], const float2* _
     const int t = otid();
     const uint32_t tu = (uint32_t)t;
     float2 c[2][R4];
-    q2_carry_first(sl, prev, c);
     const float2 wA = cmul_k(fir4_wM(tab, G::OFF_PLO, G::OFF_PHI, t), wN1());   // W_N^(2t+1)
 #pragma unroll
     for (int r = 0; r < R4; ++r) {
         const int kA = t + r * NB4;
         const float2 wk = cmul_k(wA, fir_cr<R4>(r));
         float2 xk, xm;
-        q2_carry_load(sl, prev, r + Q2_AHEAD, c);
+        q2_carry_load(sl, prev, r, c);
         fir_split(v[0][r], v[1][R4 - 1 - r], wk, xk, xm);
         q2_pair(xk, xm, at32(H0, kA), at32(H0, MH - 1 - kA), at32(H1, kA), at32(H1, MH - 1 - kA), acc[0][r],
                 acc[1][R4 - 1 - r], c[0][r], c[1][r], at32(sl, tu + (uint32_t)(r * T)),
@@ -707,7 +688,7 @@ MSG_DEV void odd_q2(const float2* tab, const float2 (&v)[2][R4], const float2* _
 __global__ void __launch_bounds__(fir8::T)
 k_fir8q(const PresetRt* __restrict__ rt, const int2* __restrict__ runs, int n_runs, int run_len,
         const float2* __restrict__ tables, const float2* __restrict__ hspec, const float* __restrict__ x_in,
-        float* __restrict__ y_out, float2* __restrict__ scratch_all, int32_t* __restrict__ ctr, int mode) {
+        float* __restrict__ y_out, float2* __restrict__ scratch_all, int32_t* __restrict__ ctr) {
     using namespace fir8;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     __shared__ int s_take;
@@ -750,10 +731,10 @@ k_fir8q(const PresetRt* __restrict__ rt, const int2* __restrict__ runs, int n_ru
             dif_split(tab, a, b);
             float2 acc[2][R4], A[R1];
             fwd_half<false>(buf, tab, a, v);
-            even_q2(tab, v, He0, He1, q2_slot(scratch, 0), j > 0 && !(mode & 1), j + 1 < j1 && !(mode & 2), acc);
+            even_q2(tab, v, He0, He1, q2_slot(scratch, 0), j > 0, j + 1 < j1, acc);
             inv_half<false>(buf, tab, acc, A);
             fwd_half<true>(buf, tab, b, v);
-            odd_q2(tab, v, Ho0, Ho1, q2_slot(scratch, 1), j > 0 && !(mode & 1), j + 1 < j1 && !(mode & 2), acc);
+            odd_q2(tab, v, Ho0, Ho1, q2_slot(scratch, 1), j > 0, j + 1 < j1, acc);
             float2 (&B)[R1] = a;                  // a is dead: its registers take B
             inv_half<true>(buf, tab, acc, B);
             const int tt = otid();                // per block: loop-invariant twiddles would be hoisted

@@ -109,18 +109,12 @@ MSG_DEV float2 fir_wM(const float2* tab, int lo, int hi, int j) {   // two-level
 MSG_DEV void fir_split(float2 zk, float2 zm, float2 wk, float2& xk, float2& xm) {
     const f2v S = add_conj(vv(zk), vv(zm));
     const f2v P = vv(cmul(wk, ff(sub_conj(vv(zk), vv(zm)))));
-#if MSG_ASM_CMUL
     f2v t, a, b;
     asm("v_pk_mul_f32 %2, %4, 0.5 op_sel:[1,0] op_sel_hi:[0,0] neg_hi:[1,0]\n\t"
         "v_pk_fma_f32 %0, %3, 0.5, %2 op_sel_hi:[1,0,1]\n\t"
         "v_pk_fma_f32 %1, %3, 0.5, %2 op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[1,0,0]"
         : "=&v"(a), "=v"(b), "=&v"(t) : "v"(S), "v"(P));
     xk = ff(a); xm = ff(b);
-#else
-    const f2v t = f2v{0.5f * P.y, -0.5f * P.x};
-    xk = ff(0.5f * S + t);
-    xm = make_float2(0.5f * S.x - t.x, t.y - 0.5f * S.y);
-#endif
 }
 
 // forward real-FFT split of bins k, M-k and the multiply-accumulate with H
@@ -139,18 +133,12 @@ MSG_DEV void fir_pair_mac(float2 zk, float2 zm, float2 wk, float2 hk, float2 hm,
 MSG_DEV void fir_pair_pre(float2& yk, float2& ym, float2 wk) {
     const f2v S = add_conj(vv(yk), vv(ym));
     const f2v Pc = vv(cmulc(ff(sub_conj(vv(yk), vv(ym))), wk));
-#if MSG_ASM_CMUL
     f2v t, a, b;
     asm("v_pk_mul_f32 %2, %4, 0.5 op_sel:[1,0] op_sel_hi:[0,0]\n\t"
         "v_pk_fma_f32 %0, %3, 0.5, %2 op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[1,0,1]\n\t"
         "v_pk_fma_f32 %1, %3, 0.5, %2 op_sel_hi:[1,0,1] neg_hi:[0,0,1]"
         : "=&v"(a), "=v"(b), "=&v"(t) : "v"(S), "v"(Pc));
     yk = ff(a); ym = ff(b);
-#else
-    const f2v t = f2v{0.5f * Pc.y, 0.5f * Pc.x};
-    yk = make_float2(0.5f * S.x - t.x, -0.5f * S.y - t.y);
-    ym = make_float2(0.5f * S.x + t.x, 0.5f * S.y - t.y);
-#endif
 }
 
 // exp(-pi i r / R3): the post-twiddle step between the butterflies' bins

@@ -20,8 +20,6 @@ static_assert(H_TILE == H_BUILD_TILE, "k_h_build tile");
 void fir_init_attrs() {
     (void)hipFuncSetAttribute((const void*)k_fir4<16384>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               Fir4Geo<16384>::LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)k_fir4s<16384>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              Fir4Geo<16384>::LDS_BYTES);
     (void)hipFuncSetAttribute((const void*)k_fir4_hconv<16384>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               Fir4Geo<16384>::LDS_BYTES);
     (void)hipFuncSetAttribute((const void*)k_fir4_irspec<16384>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -114,15 +112,6 @@ hipError_t launch_fir4(int M, unsigned grid, hipStream_t s, const PresetRt* rt, 
     return hipGetLastError();
 }
 
-hipError_t launch_fir4s(int M, unsigned grid, hipStream_t s, const PresetRt* rt, const int2* jobs,
-                        const float2* tables, const float2* hspec, const float* x_in, float* y_out, int kblk) {
-    static_assert(FIR4S_P == 16384, "k_fir4s<16384>: P = M");
-    if (M != 16384 || kblk < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_fir4s<16384>), dim3(grid), dim3(Fir4Geo<16384>::T), Fir4Geo<16384>::LDS_BYTES, s, rt, jobs,
-                       tables, hspec, x_in, y_out, kblk);
-    return hipGetLastError();
-}
-
 hipError_t launch_fir4_hpart(int M, unsigned n_parts, hipStream_t s, const PresetRt* rt, const int2* part_jobs,
                              const float2* tables, const float* hs, float2* hspec) {
     if (M != 16384) return hipErrorInvalidValue;
@@ -157,22 +146,22 @@ hipError_t launch_fir8(unsigned grid, hipStream_t s, const PresetRt* rt, const i
 // launch; each launch leaves them zero)
 hipError_t launch_fir8p(unsigned n_jobs, unsigned grid, hipStream_t s, const PresetRt* rt, const int2* jobs,
                         const float2* tables, const float2* hspec, const float* x_in, float* y_out, int32_t* ctr,
-                        int stagger, const msg_event* events, const float* grain_pool, const int32_t* ev_lo) {
+                        const msg_event* events, const float* grain_pool, const int32_t* ev_lo) {
     if (events)
         hipLaunchKernelGGL((k_fir8p<true>), dim3(grid), dim3(fir8::T), Fir4Geo<16384>::LDS_BYTES, s, rt, jobs,
-                           (int)n_jobs, tables, hspec, x_in, y_out, ctr, stagger, events, grain_pool, ev_lo);
+                           (int)n_jobs, tables, hspec, x_in, y_out, ctr, events, grain_pool, ev_lo);
     else
         hipLaunchKernelGGL((k_fir8p<false>), dim3(grid), dim3(fir8::T), Fir4Geo<16384>::LDS_BYTES, s, rt, jobs,
-                           (int)n_jobs, tables, hspec, x_in, y_out, ctr, stagger, events, grain_pool, ev_lo);
+                           (int)n_jobs, tables, hspec, x_in, y_out, ctr, events, grain_pool, ev_lo);
     return hipGetLastError();
 }
 
 // two-partition k_fir8q (fir8_fft.h): runs of run_len blocks, scratch: grid x fir8q_scratch_per_wg() float2
 hipError_t launch_fir8q(unsigned n_runs, int run_len, unsigned grid, hipStream_t s, const PresetRt* rt, const int2* runs,
                         const float2* tables, const float2* hspec, const float* x_in, float* y_out, float2* scratch,
-                        int32_t* ctr, int mode) {
+                        int32_t* ctr) {
     hipLaunchKernelGGL(k_fir8q, dim3(grid), dim3(fir8::T), Fir4Geo<16384>::LDS_BYTES, s, rt, runs, (int)n_runs, run_len,
-                       tables, hspec, x_in, y_out, scratch, ctr, mode);
+                       tables, hspec, x_in, y_out, scratch, ctr);
     return hipGetLastError();
 }
 int64_t fir8q_scratch_per_wg() { return fir8::Q2_SLOT; }

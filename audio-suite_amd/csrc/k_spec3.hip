@@ -3,13 +3,10 @@
 #include "spec3.h"
 #include "launch.h"
 #include <algorithm>
-#include <cstdlib>
 #include <cmath>
 
 void spec3_init_attrs() {
     (void)hipFuncSetAttribute((const void*)k_spec3<Spec3P18750>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              Spec3P18750::LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)k_spec3p<Spec3P18750>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               Spec3P18750::LDS_BYTES);
 }
 
@@ -30,8 +27,6 @@ bool spec3_eligible(int n, int ops, int gen_sr, double cutoff_gen, double roll, 
     if (b.ky <= P::M / 2 ? !s3_band_fits<P>(b.kz, b.ky)                       // narrow: X, Z' halves in LDS
                          : (2 * ((b.kz + 15) & ~15) > P::BUF || b.ky > P::BUF ||  // wide: Z[k], Z[M-k]; Y over X,
                             ((ops & SPEC_STRETCH) && stretch <= 1.0))) return false;   // which needs f > 1
-    static const bool wide_on = !(getenv("MSGPU_S3_WIDE") && getenv("MSGPU_S3_WIDE")[0] == '0');   // A/B switch
-    if (b.ky > P::M / 2 && !wide_on) return false;
     *kb = b.kb; *kz = b.kz; *ky = b.ky; *inv_f = b.inv_f;
     // k / f exact in float32 for every bin k < 2^15 (the wide path's gather):
     // 1 / f = q 2^-12 with q's odd part below 2^24 / 2^15
@@ -45,15 +40,9 @@ bool spec3_eligible(int n, int ops, int gen_sr, double cutoff_gen, double roll, 
 
 hipError_t launch_spec3(unsigned grid, hipStream_t s, const msg_event* events, const EventRt* ert, const PresetRt* rt,
                         const float2* tables, const int32_t* ev_list, int n_list, const float* micro_pool,
-                        float* grain_pool, int persist, int32_t* ctr) {
+                        float* grain_pool) {
     using P = Spec3P18750;
-    if (persist > 0 && ctr) {
-        grid = (unsigned)std::max(1, std::min(persist, n_list));
-        hipLaunchKernelGGL((k_spec3p<P>), dim3(grid), dim3(P::T), P::LDS_BYTES, s, events, ert, rt, tables, ev_list,
-                           n_list, micro_pool, grain_pool, ctr);
-        return hipGetLastError();
-    }
-    grid = (unsigned)((n_list + MSG_S3_EVENTS - 1) / MSG_S3_EVENTS);   // MSG_S3_EVENTS per workgroup (spec3.h)
+    grid = (unsigned)((n_list + S3_EVENTS - 1) / S3_EVENTS);   // S3_EVENTS per workgroup (spec3.h)
     hipLaunchKernelGGL((k_spec3<P>), dim3(grid), dim3(P::T), P::LDS_BYTES, s, events, ert, rt, tables, ev_list,
                        n_list, micro_pool, grain_pool);
     return hipGetLastError();

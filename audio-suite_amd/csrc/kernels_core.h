@@ -46,48 +46,14 @@ __global__ void k_plan_events(const msg_preset* __restrict__ presets, int n_pres
 #define MSG_GEN_G 8
 #endif
 constexpr int GEN_G = MSG_GEN_G;   // chunks of 64 draws classified per pass
-// Waves per event (MSG_GEN_K): wave w of an event's workgroup takes groups
-// w, w + K, w + 2K, ... of its draw stream.  Classification (the fast test and
-// the slow normals) does not depend on where the parse stands, only the walk
-// does; each wave walks its group as if no earlier slow normal reached into it,
-// and after one barrier per round every wave scans the K (count, overhang)
-// pairs; a group whose predecessor's last slow normal does reach into it walks
-// again from that overhang (rare: the last draws of a group must be slow).
-#ifndef MSG_GEN_K
-#define MSG_GEN_K 1
-#endif
-constexpr int GEN_K = MSG_GEN_K;
-// MSG_GEN_LDS=0 (tuning builds): the ziggurat tables are read through L1 and the
-// resonant rotation by cross-lane reads, so k_gen_normal allocates no LDS and its
-// waves can sit beside k_spec3's 162 KB workgroups.
-#ifndef MSG_GEN_LDS
-#define MSG_GEN_LDS 1
-#endif
-// Emission of a chunk (tuning macro): 3 = the resonant value from bases at
-// multiples of 64 samples, evaluated 64 at a time (one per lane, once per 64
-// chunks) into LDS, rotated by a 128-entry offset table; 2 = the round-3 form
-// (bases at each group's chunk starts, evaluated by lanes g < G once per group
-// of 8 chunks); rank by v_mbcnt and the valid lanes as the exec mask in both;
-// 1 = the round-2 form (the chunk's base evaluated per chunk, rank by
-// popcount); 0 = cost experiment only (raw normals, wrong output).
-#ifndef MSG_GEN_NOSLOW
-#define MSG_GEN_NOSLOW 0
-#endif
-#ifndef MSG_GEN_EMIT
-#define MSG_GEN_EMIT 3
-#endif
-#if MSG_GEN_EMIT != 1 && !MSG_GEN_LDS
-#error "MSG_GEN_EMIT 0/2/3 need MSG_GEN_LDS"
-#endif
-#if MSG_GEN_EMIT == 3 && MSG_GEN_K != 1
-#error "MSG_GEN_EMIT 3 evaluates its bases with one wave per event"
-#endif
+// One wave per event.  A chunk's resonant values come from bases at multiples
+// of 64 samples held in LDS and a 128-entry offset table; the rank of a lane
+// among the chunk's valid lanes is a v_mbcnt and the valid lanes are the exec
+// mask of the stores.
 // Jump-ahead constants and the ziggurat fast-path table (ki >> 20, wi * 2^20 as
 // float32 bits).
 struct JumpTab {
     nprng::u128 a[GEN_T]; nprng::u128 s[GEN_T]; nprng::u128 a64, s64, aG, sG;
-    nprng::u128 aW[GEN_K], sW[GEN_K];   // jump by w groups (wave w's first group)
-    nprng::u128 aR, sR;                 // jump by K groups (one round)
     uint2 kw[256]; float fif[256];
 };
 
@@ -249,54 +215,27 @@ MSG_DEV float gen_fade(const GenBasicConst& c, int j, float x) {
 // The float32 path forms the fast-path normal in float32 from the top 32 bits
 // of its 52-bit ziggurat integer (|error| <= 1 ulp of float32); slow draws and
 // RAW64 use the exact float64 product.
-#ifndef MSG_GEN_WAVES
-#define MSG_GEN_WAVES 1
-#endif
-#ifndef MSG_GEN_VGPRS
-#define MSG_GEN_VGPRS 0
-#endif
 template <bool RAW64>
-__global__ void __launch_bounds__(GEN_T * GEN_K, MSG_GEN_WAVES)
-#if MSG_GEN_VGPRS
-__attribute__((amdgpu_num_vgpr(MSG_GEN_VGPRS)))
-#endif
+__global__ void __launch_bounds__(GEN_T)
 k_gen_normal(const msg_preset* __restrict__ presets, const msg_event* __restrict__ events,
              const PresetRt* __restrict__ rt, const int32_t* __restrict__ ev_list, int n_list,
              nprng::Zig z, const JumpTab* __restrict__ jt, float* __restrict__ pool,
              double* __restrict__ pool64, const int64_t* __restrict__ off64) {
-#if MSG_GEN_LDS
     __shared__ uint64_t s_ki[256];
     __shared__ double s_wi[256];
     __shared__ uint2 s_kw[256];          // (ki >> 20, wi * 2^20 as float32 bits): the fast path's one read
     __shared__ float s_fif[256];         // fi as float32: the slow path's wedge test
-#if MSG_GEN_EMIT == 3
     __shared__ float4 s_rot[128];        // resonant: (cos, sin)(2 pi r f/sr), 0.9 * 2^(r k_ring), 0.25 * 2^(r k_exc), r = i
     __shared__ float4 s_base[64];        // resonant: (sin, cos, 2^(j k_ring), 2^(j k_exc)) at j = 64 (q0 + i)
-#elif MSG_GEN_EMIT == 2
-    __shared__ float4 s_rot[128];        // resonant: (cos, sin)(2 pi r f/sr), 0.9 * 2^(r k_ring), 0.25 * 2^(r k_exc), r = i - 64
-    __shared__ float4 s_grp[GEN_K][GEN_G];   // resonant, per wave: (sin, cos, 2^(j k_ring), 2^(j k_exc)) at j = group start + 64 g
-#else
-    __shared__ float4 s_rot[64];         // resonant: (cos, sin)(2 pi r f/sr), 2^(r k_ring), 2^(r k_exc), r < 64
-#endif
-#else
-    const uint64_t* __restrict__ s_ki = z.ki;
-    const double* __restrict__ s_wi = z.wi;
-    const uint2* __restrict__ s_kw = jt->kw;
-    const float* __restrict__ s_fif = jt->fif;
-#endif
     const int li = blockIdx.x;
     if (li >= n_list) return;
     const int lane = (int)(threadIdx.x & (GEN_T - 1));
-    const int wv = GEN_K == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x / GEN_T));
-    __shared__ int2 s_carry[2][GEN_K];   // GEN_K > 1, per round (parity) and wave: (normals, overhang)
-#if MSG_GEN_LDS
-    for (int i = (int)threadIdx.x; i < 256; i += GEN_T * GEN_K) {
+    for (int i = (int)threadIdx.x; i < 256; i += GEN_T) {
         s_ki[i] = z.ki[i];
         s_wi[i] = z.wi[i];
         s_kw[i] = jt->kw[i];
         s_fif[i] = jt->fif[i];
     }
-#endif
     const msg_event& e = events[ev_list[li]];
     const msg_preset& pr = presets[e.preset];
     const PresetRt& r = rt[e.preset];
@@ -320,47 +259,21 @@ k_gen_normal(const msg_preset* __restrict__ presets, const msg_event* __restrict
     const int sigma = (int)(0.0025 * n) > 1 ? (int)(0.0025 * n) : 1;
     c.inv_sigma = (float)(1.0 / (double)sigma);
     // Resonant strike: sample j = j0 + r of a chunk (j0 = samples already
-    // emitted, r = the lane's rank) from the chunk's uniform sin/cos and decay
-    // at j0 and the per-rank rotation/decay table (angle addition, one ds_read
-    // per sample instead of the phase reduction, a sine and two exponentials).
-#if MSG_GEN_EMIT == 3
-    // The value at j = B + t (B = 64 floor(j0 / 64) for the chunk starting at j0,
-    // t in [0, 127)) is the rotation of the base's (sin, cos, decays) by the
-    // offset table entry t, with the 0.9 and 0.25 gains folded into the table.
+    // emitted, r = the lane's rank) is the value at j = B + t, B = 64 floor(j0 / 64),
+    // t in [0, 127): the rotation of the base's (sin, cos, decays) at B by the
+    // offset table entry t, with the 0.9 and 0.25 gains folded into the table
+    // (angle addition, two ds_reads per sample instead of the phase reduction, a
+    // sine and two exponentials).  The bases are evaluated 64 at a time, one per
+    // lane, once per 64 chunks.
     int q0 = -64;                         // s_base holds the bases 64 (q0 + i), i < 64
     if (!RAW64 && c.mode == MSG_GEN_RESONANT) {
-        for (int i = (int)threadIdx.x; i < 128; i += GEN_T * GEN_K) {
+        for (int i = (int)threadIdx.x; i < 128; i += GEN_T) {
             const float rf = (float)i;
             const float2 sc = ring_sincos(rf, c.fa, c.fb);
             s_rot[i] = make_float4(sc.y, sc.x, 0.9f * __builtin_amdgcn_exp2f(rf * c.k_ring),
                                    0.25f * __builtin_amdgcn_exp2f(rf * c.k_exc));
         }
     }
-#elif MSG_GEN_EMIT == 2
-    // Two-level form: the value at j = B + t (B = a group's chunk base, |t| < 64
-    // or t in [-64, 0) after slow draws shifted the chunk) is the rotation of the
-    // base's (sin, cos, decays) by the offset table entry t, with the 0.9 and
-    // 0.25 gains folded into the table.
-    if (!RAW64 && c.mode == MSG_GEN_RESONANT) {
-        for (int i = (int)threadIdx.x; i < 128; i += GEN_T * GEN_K) {
-            const float rf = (float)(i - 64);
-            const float2 sc = ring_sincos(rf, c.fa, c.fb);
-            s_rot[i] = make_float4(sc.y, sc.x, 0.9f * __builtin_amdgcn_exp2f(rf * c.k_ring),
-                                   0.25f * __builtin_amdgcn_exp2f(rf * c.k_exc));
-        }
-    }
-#else
-    float4 rot = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!RAW64 && c.mode == MSG_GEN_RESONANT) {
-        const float rf = (float)lane;
-        const float ph = ring_phase(rf, c.fa, c.fb);
-        rot = make_float4(__builtin_amdgcn_cosf(ph), __builtin_amdgcn_sinf(ph),
-                          __builtin_amdgcn_exp2f(rf * c.k_ring), __builtin_amdgcn_exp2f(rf * c.k_exc));
-#if MSG_GEN_LDS
-        s_rot[lane] = rot;
-#endif
-    }
-#endif
 
     // default_rng(seed + i): every lane computes the (uniform) seed state.
     const nprng::Pcg64 g0 = nprng::default_rng((uint64_t)(pr.seed + e.index));
@@ -377,19 +290,14 @@ k_gen_normal(const msg_preset* __restrict__ presets, const msg_event* __restrict
     constexpr int G = GEN_G;
     nprng::u128 st[G];
     st[0] = jt->a[lane] * g0.state + inc * jt->s[lane];   // state after lane+1 steps
-    if (GEN_K > 1) st[0] = jt->aW[wv] * st[0] + inc * jt->sW[wv];   // + wv groups
 #pragma unroll
     for (int g = 1; g < G; ++g) st[g] = a64 * st[g - 1] + c64;
-    const nprng::u128 aG = GEN_K > 1 ? jt->aR : jt->aG;   // the next group of this wave
-    const nprng::u128 cG = inc * (GEN_K > 1 ? jt->sR : jt->sG);
-#if MSG_GEN_LDS
+    const nprng::u128 aG = jt->aG;   // the next group
+    const nprng::u128 cG = inc * jt->sG;
     __syncthreads();
-#endif
 
-    int produced = 0;   // normals of all groups walked so far (workgroup-uniform)
+    int produced = 0;   // normals of all groups walked so far
     int local = 0;      // first lane of the next group not consumed by an earlier slow normal
-    int rpar = 0;       // s_carry buffer of this round
-    (void)rpar;
     while (produced < n) {
         using XT = typename std::conditional<RAW64, double, float>::type;
         uint64_t rabs[G], F[G];
@@ -431,9 +339,6 @@ k_gen_normal(const msg_preset* __restrict__ presets, const msg_event* __restrict
             F[g] = __ballot(fast);
             if (!fast) slow |= 1u << g;
         }
-#if MSG_GEN_NOSLOW                                // cost experiment only: slow draws left as classified
-        slow = 0;
-#endif
         while (slow) {                            // divergent: each lane walks its own slow draws
             const int gs = __builtin_ctz(slow);
             slow &= slow - 1;
@@ -453,55 +358,13 @@ k_gen_normal(const msg_preset* __restrict__ presets, const msg_event* __restrict
             for (int g = 0; g < G; ++g)
                 if (gs == g) { x[g] = (XT)v; consumed[g] = cn; }
         }
-        // the walk: which lanes of each chunk start a normal (vb), and this wave's
-        // first output index pw
+        // the walk: which lanes of each chunk start a normal (vb)
         uint32_t vb;
-        int cnt, pw;
-        if constexpr (GEN_K == 1) {
-            local = gen_walk<G>(F, consumed, local, vb, cnt);
-            pw = produced;
-            produced += cnt;
-        } else {
-            int lout = gen_walk<G>(F, consumed, 0, vb, cnt);   // as if nothing reaches into the group
-            if (lane == 0) s_carry[rpar][wv] = make_int2(cnt, lout);
-            __syncthreads();
-            pw = produced;
-            int lin = local;
-#pragma unroll 1
-            for (int j = 0; j < GEN_K; ++j) {
-                if (lin != 0) {                   // workgroup-uniform: group j starts inside a slow normal
-                    if (wv == j) {
-                        lout = gen_walk<G>(F, consumed, lin, vb, cnt);
-                        if (lane == 0) s_carry[rpar][j] = make_int2(cnt, lout);
-                    }
-                    __syncthreads();
-                }
-                const int2 cj = s_carry[rpar][j];
-                if (wv == j) pw = produced;
-                produced += cj.x;
-                lin = cj.y;
-            }
-            local = lin;
-            rpar ^= 1;
-        }
-#if MSG_GEN_EMIT == 3
+        int cnt;
+        int pc = produced;                        // output index of the chunk's first normal
+        local = gen_walk<G>(F, consumed, local, vb, cnt);
+        produced += cnt;
         const bool reson = !RAW64 && c.mode == MSG_GEN_RESONANT;
-#elif MSG_GEN_EMIT == 2
-        // resonant: lanes g < G evaluate the group's chunk bases p0 + 64 g (one set
-        // of transcendentals per group instead of per chunk)
-        const bool reson = !RAW64 && c.mode == MSG_GEN_RESONANT;
-        const int p0 = pw;
-        if (reson) {
-            if (lane < G) {
-                const float jb = (float)(p0 + 64 * lane);
-                const float2 sc = ring_sincos(jb, c.fa, c.fb);
-                s_grp[wv][lane] = make_float4(sc.x, sc.y, __builtin_amdgcn_exp2f(fmaxf(jb * c.k_ring, -126.f)),
-                                              __builtin_amdgcn_exp2f(fmaxf(jb * c.k_exc, -126.f)));
-            }
-            __syncthreads();                      // orders the LDS writes before the reads
-        }
-#endif
-        int pc = pw;                              // output index of the chunk's first normal
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const uint64_t valid = __ballot((vb >> g) & 1u);
@@ -511,9 +374,7 @@ k_gen_normal(const msg_preset* __restrict__ presets, const msg_event* __restrict
                     const int j = pc + __popcll(valid & ((1ULL << lane) - 1));
                     if (j < n) out64[j] = x[g];
                 }
-            }
-#if MSG_GEN_EMIT == 3
-            else {
+            } else {
                 // rank among the valid lanes (v_mbcnt), the valid mask as the exec mask
                 const int rk = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(valid >> 32),
                                                               __builtin_amdgcn_mbcnt_lo((uint32_t)valid, 0u));
@@ -544,77 +405,6 @@ k_gen_normal(const msg_preset* __restrict__ presets, const msg_event* __restrict
                     ob[rk] = gen_basic_sample(c, pc + rk, (float)x[g]);
                 }
             }
-#elif MSG_GEN_EMIT == 2
-            else {
-                // rank among the valid lanes (v_mbcnt), the valid mask as the exec mask
-                const int rk = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(valid >> 32),
-                                                              __builtin_amdgcn_mbcnt_lo((uint32_t)valid, 0u));
-                const bool vl = __builtin_amdgcn_inverse_ballot_w64(valid);
-                const int room = n - pc;          // uniform
-                float* __restrict__ ob = out + pc;
-                if (reson) {
-                    // j = pc + rk = B_g + (d + rk), d = pc - B_g in [-64, 0]
-                    const int d = pc - (p0 + 64 * g);
-                    float4 u;
-                    int off;
-                    if (d >= -64) {
-                        u = s_grp[wv][g];
-                        off = d + 64;
-                    } else {                          // a slow normal spanned > 64 draws: exact base
-                        const float j0 = (float)pc;
-                        const float2 sc = ring_sincos(j0, c.fa, c.fb);
-                        u = make_float4(sc.x, sc.y, __builtin_amdgcn_exp2f(fmaxf(j0 * c.k_ring, -126.f)),
-                                        __builtin_amdgcn_exp2f(fmaxf(j0 * c.k_exc, -126.f)));
-                        off = 64;
-                    }
-                    const bool edge = pc < c.fade || pc + 64 > c.n - c.fade;
-                    if (vl && rk < room) {
-                        const float4 tb = s_rot[rk + off];
-                        float v = fmaf(u.x, tb.x, u.y * tb.y) * (u.z * tb.z) + x[g] * (u.w * tb.w);
-                        if (edge) v = gen_fade(c, pc + rk, v);
-                        ob[rk] = v;
-                    }
-                } else if (vl && rk < room) {
-                    ob[rk] = gen_basic_sample(c, pc + rk, (float)x[g]);
-                }
-            }
-#elif MSG_GEN_EMIT == 0
-            else {                                // cost experiment only: raw normals, no generator formula
-                const int rk = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(valid >> 32),
-                                                              __builtin_amdgcn_mbcnt_lo((uint32_t)valid, 0u));
-                if (__builtin_amdgcn_inverse_ballot_w64(valid) && rk < n - pc) out[pc + rk] = (float)x[g];
-            }
-#else
-            else if (c.mode == MSG_GEN_RESONANT) {
-                // chunk-uniform phase and decays at j0 = pc
-                const float j0 = (float)pc;
-                const float ph0 = ring_phase(j0, c.fa, c.fb);
-                const float s0 = __builtin_amdgcn_sinf(ph0), c0 = __builtin_amdgcn_cosf(ph0);
-                const float dA = __builtin_amdgcn_exp2f(fmaxf(j0 * c.k_ring, -126.f));
-                const float dE = __builtin_amdgcn_exp2f(fmaxf(j0 * c.k_exc, -126.f));
-                const bool edge = pc < c.fade || pc + 64 > c.n - c.fade;
-                const int rk = __popcll(valid & ((1ULL << lane) - 1));
-#if MSG_GEN_LDS
-                const float4 tb = s_rot[rk];
-#else
-                const float4 tb = make_float4(__shfl(rot.x, rk), __shfl(rot.y, rk), __shfl(rot.z, rk),
-                                              __shfl(rot.w, rk));   // every lane: lane rk holds rank rk's rotation
-#endif
-                if ((valid >> lane) & 1) {
-                    const int j = pc + rk;
-                    if (j < n) {
-                        float v = 0.9f * fmaf(s0, tb.x, c0 * tb.y) * (dA * tb.z) + 0.25f * x[g] * (dE * tb.w);
-                        if (edge) v = gen_fade(c, j, v);
-                        out[j] = v;
-                    }
-                }
-            } else {
-                if ((valid >> lane) & 1) {
-                    const int j = pc + __popcll(valid & ((1ULL << lane) - 1));
-                    if (j < n) out[j] = gen_basic_sample(c, j, (float)x[g]);
-                }
-            }
-#endif
             pc += __popcll(valid);
         }
 #pragma unroll
@@ -674,17 +464,10 @@ k_er_gains(const msg_preset* __restrict__ presets, const PresetRt* __restrict__ 
 // ---------------------------------------------------------------------------
 // Overlap-add of placed grains (event order) x ADSR -> mono a[t].
 // ---------------------------------------------------------------------------
-// Traversal order against the Infinity Cache (tuning A/B): MSG_OLA_REV = 1
-// walks each XCD's job range backwards, so overlap-add starts on the most
-// recently written end of the spectral kernel's grains (measured neutral,
+// Traversal order: each XCD's job range forwards (walking it backwards, from the
+// most recently written end of the spectral kernel's grains, measured neutral,
 // profiles/r03ak_traversal_ab.txt).
-#ifndef MSG_OLA_REV
-#define MSG_OLA_REV 0
-#endif
-MSG_DEV int job_order(int rev) {
-    const int b = xcd_block(blockIdx.x, gridDim.x);
-    return rev ? (int)gridDim.x - 1 - b : b;
-}
+MSG_DEV int job_order() { return xcd_block(blockIdx.x, gridDim.x); }
 
 // One OLA_TILE tile [t0, t0 + OLA_TILE) of preset r: the placed grains in event
 // order times the ADSR (MS:742-764), into its mono buffer.
@@ -757,7 +540,7 @@ __global__ void __launch_bounds__(OLA_T)
 k_ola_env(const msg_event* __restrict__ events, const PresetRt* __restrict__ rt,
           const int32_t* __restrict__ tile_begin, int n_presets,
           const float* __restrict__ grain_pool, float* __restrict__ mono) {
-    const int b = job_order(MSG_OLA_REV);
+    const int b = job_order();
     const int p = find_preset(tile_begin, n_presets, b);
     const PresetRt& r = rt[p];
     ola_tile(events, r, (int64_t)(b - r.tile_begin) * OLA_TILE, grain_pool, mono);

@@ -9,12 +9,12 @@
 // floor of an exact-twiddle FFT is 5-7e-6 RMS there (tools/fir_error_model.py),
 // next to the 1e-5 tolerance.  Such presets get the FIR again in float64:
 //
-//   k_stereo_fused / k_stereo_max (first pass, kernels_stereo.h) adds per
+//   k_stereo_max and k_stereo_pred (first pass, kernels_stereo.h) add per
 //     preset sum y^2 and sum (1 + (d y)^2)^-2 (the share of samples the clip
-//     leaves in its linear range) over the float32 y, in tile order, predicts
+//     leaves in its linear range) over the float32 y, in tile order, predict
 //     the float32 error from them (fir64_pred, rt.h: eps32 rms(y) x
 //     sqrt(share) x the clip's slope and the peak scale, within 2-3x of the
-//     exact-twiddle float32 error, tools/fir_error_model.py) and flags every
+//     exact-twiddle float32 error, tools/fir_error_model.py) and flag every
 //     preset above FIR64_PRED (flag64);
 //   k_fir64_flag gives every flagged preset a slot, in batch order, and resets
 //     its stereo peak;
@@ -26,10 +26,9 @@
 //              (Q + 1 float64 transforms on the LDS engine of the grain chain)
 //              -> irfft -> y as float32 (its rounding: ~1e-8 RMS);
 // then the odd-length stereo rotation and the peak pass run again for the
-// slots (kernels_stereo_odd.h, k_stereo_remax) and k_stereo_out_list writes
-// their output (k_stereo_fused deferred it).  A preset's route depends only on
-// its own render, never on the batch it shares (at most 128 slots
-// had been served, in batch order).
+// slots (kernels_stereo_odd.h, k_stereo_remax) before k_stereo_out writes the
+// output.  A preset's route depends only on its own render, never on the batch
+// it shares (at most 128 slots had been served, in batch order).
 // Every kernel of the chain walks a virtual (slot, unit) space in a grid-stride
 // loop and skips units of empty slots, so a batch without flagged presets (C3,
 // C4, C5, the shipped presets but wavelet_mist) pays a few microseconds.

@@ -34,11 +34,9 @@ void spec3_init_attrs();
 bool spec3_tables(std::vector<float>& out);
 bool spec3_eligible(int n, int ops, int gen_sr, double cutoff_gen, double roll, double stretch, int64_t float_off,
                     int32_t* kb, int32_t* kz, int32_t* ky, double* inv_f, int32_t* exact32);
-// persist > 0: k_spec3p on that many workgroups (one per CU) with the per-XCD
-// event counters ctr ((MSG_XCDS + 1) x S3P_CTR int32, zero; left zero)
 hipError_t launch_spec3(unsigned grid, hipStream_t s, const msg_event* events, const EventRt* ert, const PresetRt* rt,
                         const float2* tables, const int32_t* ev_list, int n_list, const float* micro_pool,
-                        float* grain_pool, int persist = 0, int32_t* ctr = nullptr);
+                        float* grain_pool);
 
 void fir_init_attrs();
 // the float64 space FIR of heavily saturated renders (kernels_fir64.h): flag, h, H_q, blocks
@@ -78,8 +76,6 @@ hipError_t launch_fir2(int M, unsigned grid, hipStream_t s, const PresetRt* rt, 
 bool fir4_tables_host(int M, std::vector<float>& out);
 hipError_t launch_fir4(int M, unsigned grid, hipStream_t s, const PresetRt* rt, const int2* jobs,
                        const float2* tables, const float2* hspec, const float* x_in, float* y_out);
-// streaming variant (B = P = 16384, Q <= 2): jobs (preset, first block), kblk blocks per workgroup
-constexpr int FIR4S_P = 16384;
 // partition spectra on the k_fir4 engine (fir4_fft.h): k_fir4_hpart over the (preset, q) jobs
 hipError_t launch_fir4_hpart(int M, unsigned n_parts, hipStream_t s, const PresetRt* rt, const int2* part_jobs,
                              const float2* tables, const float* hs, float2* hspec);
@@ -101,7 +97,7 @@ hipError_t launch_fir8(unsigned grid, hipStream_t s, const PresetRt* rt, const i
                        const float2* hspec, const float* x_in, float* y_out);
 hipError_t launch_fir8p(unsigned n_jobs, unsigned grid, hipStream_t s, const PresetRt* rt, const int2* jobs,
                         const float2* tables, const float2* hspec, const float* x_in, float* y_out, int32_t* ctr,
-                        int stagger, const msg_event* events, const float* grain_pool,
+                        const msg_event* events, const float* grain_pool,
                         const int32_t* ev_lo);   // events: null if no ola_fir preset; ev_lo: per job, the
                                                  // first event reaching its segment
 // two partitions of N / 2 taps on the N = 65536 engine (fir8_fft.h k_fir8q): B = P = 32768,
@@ -109,7 +105,7 @@ hipError_t launch_fir8p(unsigned n_jobs, unsigned grid, hipStream_t s, const Pre
 constexpr int FIR8Q_P = FIR8_N / 2;
 hipError_t launch_fir8q(unsigned n_runs, int run_len, unsigned grid, hipStream_t s, const PresetRt* rt, const int2* runs,
                         const float2* tables, const float2* hspec, const float* x_in, float* y_out, float2* scratch,
-                        int32_t* ctr, int mode = 0);   // mode: timing experiments only (MSGPU_FIR8Q_MODE)
+                        int32_t* ctr);
 int64_t fir8q_scratch_per_wg();
 hipError_t launch_fir8_hconv(unsigned n_presets, hipStream_t s, const PresetRt* rt, const int32_t* list,
                              const float2* tables, const int32_t* er_off, const double* er_gain, float2* hspec);
@@ -117,8 +113,6 @@ hipError_t launch_fir8_spec64(unsigned n_jobs, hipStream_t s, const int64_t* job
                               const double* src, float2* hspec);
 hipError_t launch_fir8_spec32(unsigned n_jobs, hipStream_t s, const int64_t* jobs, const float2* tables,
                               const float* src, float2* hspec);
-hipError_t launch_fir4s(int M, unsigned grid, hipStream_t s, const PresetRt* rt, const int2* jobs,
-                        const float2* tables, const float2* hspec, const float* x_in, float* y_out, int kblk);
 
 void fft_bench_init_attrs();
 hipError_t launch_fft_bench(bool po2, unsigned grid, int lds_bytes, hipStream_t s, const RealPlan* plans, int plan,
@@ -161,17 +155,11 @@ hipError_t launch_stereo_max(unsigned n_tiles, hipStream_t s, const PresetRt* rt
 // after k_stereo_max, with the float64 FIR on: per preset the predictor's sums (tile order) and flag64
 hipError_t launch_stereo_pred(unsigned n_presets, hipStream_t s, const PresetRt* rt, const int32_t* st_begin,
                               int n_tiles, const unsigned* maxbits, const StereoSync& sy);
-hipError_t launch_stereo_fused(unsigned grid, unsigned n_tiles, hipStream_t s, const PresetRt* rt,
-                               const int32_t* st_begin, int n_presets, const float* y, unsigned* maxbits,
-                               const StereoSync& sy, int32_t* ctr, float* out);
 hipError_t launch_stereo_out(unsigned n_tiles, hipStream_t s, const PresetRt* rt, const int32_t* st_begin, int n_presets,
                              const float* y, const float* r2, const unsigned* maxbits, float* out);
 hipError_t launch_stereo_remax(unsigned grid, hipStream_t s, const PresetRt* rt, const int32_t* st_count,
                                const int32_t* list, const int32_t* n_list, int tmax, const float* y, const float* r2,
                                unsigned* maxbits);
-hipError_t launch_stereo_out_list(unsigned grid, hipStream_t s, const PresetRt* rt, const int32_t* st_count,
-                                  const int32_t* list, const int32_t* n_list, int tmax, const float* y, const float* r2,
-                                  const unsigned* maxbits, float* out);
 
 // odd-length stereo rotation (kernels_stereo_odd.h): Bluestein through M = pow2 >= 2n-1
 void stereo_odd_init_attrs();

@@ -33,9 +33,6 @@
 #include "launch.h"
 #include "host_pool.h"
 #include "tap_sort.h"
-#ifndef MSG_TAP_RADIX
-#define MSG_TAP_RADIX 1   // tuning A/B: 0 = std::sort of the tap keys
-#endif
 #include "../../include/msgpu.h"
 
 namespace {
@@ -62,15 +59,6 @@ struct DevBuf {
     }
     void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
 };
-
-// ensure() that leaves a new allocation zeroed (counters and flags the kernels reset themselves)
-template <class T>
-static hipError_t ensure_zeroed(DevBuf<T>& b, size_t n, hipStream_t s) {
-    if (n <= b.cap && b.p) return hipSuccess;
-    hipError_t e = b.ensure(n);
-    if (e != hipSuccess) return e;
-    return hipMemsetAsync(b.p, 0, b.cap * sizeof(T), s);
-}
 
 // Pinned staging for a batch's host -> device uploads.  Every per-batch input
 // (presets, events, runtime records, job lists, IR bank ...) is packed into one
@@ -229,11 +217,6 @@ struct msg_ctx {
     bool fir8q = true;           // msg_fir: 32 k < M <= 64 k taps as two partitions on k_fir8q (MSGPU_FIR8Q=0: off)
     int n_cu = 256;              // compute units (persistent grids)
     int fir8p_cus = 0;           // persistent FIR workgroups (MSGPU_FIR8P_CUS, A/B; 0: one per CU)
-    int fir8p_stagger = 0;       // k_fir8p: every other workgroup starts this many 10-ns ticks later (MSGPU_FIR8P_STAGGER)
-    // k_spec3 events (MSGPU_SPEC3P): 0 two per workgroup (the chain), 1 persistent
-    // workgroups, one per CU, events from per-XCD counters (k_spec3p); > 1: that
-    // many persistent workgroups (A/B)
-    int spec3p = 0;
     // overlap-add inside k_fir8p's loads (PresetRt::ola_fir) for batches whose k_fir8p
     // presets' grains total at most ola_fir_density x their frames (MSGPU_OLA_FIR=0: never)
     bool ola_fir = true;
@@ -243,14 +226,6 @@ struct msg_ctx {
     int h_early = 2;
     bool er_dev = true;          // ER gains drawn on the device (k_er_gains; MSGPU_ER_DEV=0: on the host plan)
     double ola_fir_density = 1.25;
-    // Q <= 2 presets on the streaming k_fir4s (MSGPU_FIR4S=1; off by default: at
-    // C3's 24 blocks per preset its H re-reads miss L2 and cancel the saved transforms)
-    bool fir4s = false;
-    int fir4s_wgs = 1024;        // k_fir4s workgroups a batch aims for (MSGPU_FIR4S_WGS)
-    // at most this many blocks per k_fir4s workgroup (MSGPU_FIR4S_K): every block
-    // re-reads H_0 and H_1 (2 x 128 KB), so the workgroups running at once on an
-    // XCD must share presets for those reads to hit its 4 MB L2
-    int fir4s_kmax = 6;
     float2* d_spec_ct_tab[SPEC_CT_PLANS] = {};   // compile-time spectral plans (spec_ct.h)
     float2* d_spec3_tab = nullptr;               // band-pruned spectral kernel (spec3.h)
     Slice<int32_t> spec3_list;
@@ -295,16 +270,8 @@ struct msg_ctx {
     Slice<int32_t> st_count, odd_list, odd_cnt;
     DevBuf<double> f64_stats;                   // per preset: sum y^2, sum (1 + (d y)^2)^-2
     DevBuf<int32_t> f64_flag, f64_slot_preset, f64_nslots;
-    // stereo pass (kernels_stereo.h): the fused persistent launch (MSGPU_STEREO_FUSED=1;
-    // off by default) and its per-preset sync state, per-tile partial sums, counters
-    bool stereo_fused = false;          // measured slower than the two launches
-    int st_wgs = 4;                     // k_stereo_fused workgroups per CU (MSGPU_STEREO_WGS)
-    uint32_t st_epoch = 0;
-    DevBuf<int32_t> st_done, st_ctr;
-    DevBuf<uint32_t> st_ready;
-    DevBuf<double> st_part;
+    DevBuf<double> st_part;             // stereo pass (kernels_stereo.h): per-tile partial sums
     DevBuf<int32_t> fir8_ctr;           // k_fir8p's per-XCD block counters
-    DevBuf<int32_t> spec3_ctr;          // k_spec3p's per-XCD event counters
     DevBuf<float> f64_h;
     DevBuf<double2> f64_hs;
     // float64 grain chain (kernels_grain64.h)
@@ -530,14 +497,10 @@ static double bessel_j(int m, double x) {
 // built in the time domain by k_h_build, so any N with P < N qualifies).
 // fir8: also consider N = 65536 with one partition (k_fir8: two half-size
 // transforms per transform of N, P = M).
-// stream: when non-null, also consider k_fir4s (N = 32768, P = B = 16384, Q <= 2:
-// one forward and one inverse transform per block plus, for Q = 2, one forward
-// per workgroup of kblk blocks) and report whether it won.
 // M8: the length of the filter k_fir8 would apply (its spectrum holds every
 // in-range ER tap and the whole IR, so it can be longer than an M capped at
 // out_n); the 65536-point candidate needs M8 + B - 1 <= N or it wraps.
-static void choose_fir(int64_t M, int64_t n, int& N, int& P, int& Q, bool fir8, bool* stream = nullptr,
-                       int kblk = 1, int64_t M8 = -1) {
+static void choose_fir(int64_t M, int64_t n, int& N, int& P, int& Q, bool fir8, int64_t M8 = -1) {
     if (M8 < M) M8 = M;
     double best = 1e300;
     N = FIR_NMAX; P = (int)std::min<int64_t>(M, FIR_NMAX / 2); Q = (int)((M + P - 1) / P);
@@ -557,16 +520,6 @@ static void choose_fir(int64_t M, int64_t n, int& N, int& P, int& Q, bool fir8, 
         const int64_t blocks = (n + B - 1) / B;
         const double cost = (double)blocks * 2 * FIR8_N * 16 + (double)blocks * FIR8_N * 4.0;
         if (cost < best) { best = cost; N = FIR8_N; P = (int)M8; Q = 1; }
-    }
-    if (stream) {
-        *stream = false;
-        const int NN = 2 * FIR4S_P, lg = 15;
-        const int64_t q = (M + FIR4S_P - 1) / FIR4S_P;
-        if (q <= 2) {
-            const int64_t blocks = (n + FIR4S_P - 1) / FIR4S_P;
-            const double cost = (double)blocks * (2.0 + (q - 1) / (double)kblk) * NN * lg + (double)blocks * NN * 4.0;
-            if (cost < best) { best = cost; N = NN; P = FIR4S_P; Q = (int)q; *stream = true; }
-        }
     }
 }
 
@@ -672,14 +625,6 @@ static hipError_t fir8_counters(msg_ctx* ctx, hipStream_t s) {
     return hipMemsetAsync(ctx->fir8_ctr.p, 0, sizeof(int32_t) * ctx->fir8_ctr.cap, s);
 }
 
-// k_spec3p's per-XCD event counters: zeroed once; every launch leaves them zero
-static hipError_t spec3_counters(msg_ctx* ctx, hipStream_t s) {
-    if (ctx->spec3_ctr.p) return hipSuccess;
-    const hipError_t e = ctx->spec3_ctr.ensure((size_t)(MSG_XCDS + 1) * S3P_CTR);
-    if (e != hipSuccess) return e;
-    return hipMemsetAsync(ctx->spec3_ctr.p, 0, sizeof(int32_t) * ctx->spec3_ctr.cap, s);
-}
-
 // Wait for the context's last batch (not the whole device: other contexts'
 // streams keep running).
 static hipError_t wait_last(msg_ctx* ctx) {
@@ -736,12 +681,6 @@ msg_ctx* msg_create(int device_ordinal) {
     jt.a64 = j64.a; jt.s64 = j64.s;
     const nprng::Jump jG = nprng::jump_of((uint64_t)GEN_T * GEN_G);
     jt.aG = jG.a; jt.sG = jG.s;
-    for (int w = 0; w < GEN_K; ++w) {
-        const nprng::Jump jw = nprng::jump_of((uint64_t)GEN_T * GEN_G * w);
-        jt.aW[w] = jw.a; jt.sW[w] = jw.s;
-    }
-    const nprng::Jump jR = nprng::jump_of((uint64_t)GEN_T * GEN_G * GEN_K);
-    jt.aR = jR.a; jt.sR = jR.s;
     for (int i = 0; i < 256; ++i) {
         const float w = (float)(zig_wi_double[i] * 1048576.0);
         uint32_t wb;
@@ -773,22 +712,15 @@ msg_ctx* msg_create(int device_ordinal) {
     if (const char* e = getenv("MSGPU_FIR8P")) ctx->fir8p = atoi(e);
     if (const char* e = getenv("MSGPU_FIR8Q")) ctx->fir8q = e[0] != '0';
     if (const char* e = getenv("MSGPU_FIR8P_CUS")) ctx->fir8p_cus = std::max(0, atoi(e));
-    if (const char* e = getenv("MSGPU_FIR8P_STAGGER")) ctx->fir8p_stagger = std::max(0, atoi(e));
-    if (const char* e = getenv("MSGPU_SPEC3P")) ctx->spec3p = atoi(e);
     if (const char* e = getenv("MSGPU_OLA_FIR")) ctx->ola_fir = e[0] != '0';
     if (const char* e = getenv("MSGPU_H_EARLY")) ctx->h_early = atoi(e);
     if (const char* e = getenv("MSGPU_ER_DEV")) ctx->er_dev = e[0] != '0';
     if (const char* e = getenv("MSGPU_OLA_FIR_DENSITY")) ctx->ola_fir_density = atof(e);
-    if (const char* e = getenv("MSGPU_STEREO_FUSED")) ctx->stereo_fused = e[0] != '0';
-    if (const char* e = getenv("MSGPU_STEREO_WGS")) ctx->st_wgs = std::max(1, std::min(16, atoi(e)));
     {
         int cu = 0;
         if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cu >= MSG_XCDS)
             ctx->n_cu = cu;
     }
-    if (const char* e = getenv("MSGPU_FIR4S")) ctx->fir4s = e[0] == '1';
-    if (const char* e = getenv("MSGPU_FIR4S_WGS")) ctx->fir4s_wgs = std::max(1, atoi(e));
-    if (const char* e = getenv("MSGPU_FIR4S_K")) ctx->fir4s_kmax = std::max(2, std::min(64, atoi(e)));
     for (int i = 0; i < SPEC_CT_PLANS; ++i) {
         std::vector<float> tab;
         if (!spectral_ct_tables(i, tab) || !up(ctx->d_spec_ct_tab[i], reinterpret_cast<float2*>(tab.data()),
@@ -855,9 +787,9 @@ void msg_destroy(msg_ctx* ctx) {
     ctx->micro.release(); ctx->grain.release();
     ctx->mono_a.release(); ctx->mono_y.release(); ctx->hspec.release();
     ctx->hscratch.release();
-    ctx->f64_stats.release(); ctx->f64_flag.release(); ctx->st_done.release(); ctx->st_ctr.release();
-    ctx->fir8_ctr.release(); ctx->spec3_ctr.release();
-    ctx->st_ready.release(); ctx->st_part.release(); ctx->f64_slot_preset.release(); ctx->f64_nslots.release();
+    ctx->f64_stats.release(); ctx->f64_flag.release();
+    ctx->fir8_ctr.release();
+    ctx->st_part.release(); ctx->f64_slot_preset.release(); ctx->f64_nslots.release();
     ctx->f64_h.release(); ctx->f64_hs.release();
     for (void* p : ctx->plans64.allocs) hipFree(p);
     ctx->plans64.dev.release();
@@ -1082,8 +1014,7 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
         HIPCHK(ctx, hipMemcpyAsync(ctx->sf_irjobs.p, job, sizeof(job), hipMemcpyHostToDevice, s));
         HIPCHK(ctx, launch_fir8_spec32(2, s, ctx->sf_irjobs.p, ctx->d_fir4tab, ctx->sf_hf.p, ctx->sf_hspec.p));
         HIPCHK(ctx, launch_fir8q((unsigned)runs.size(), run_len, grid, s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab,
-                                 ctx->sf_hspec.p, x_dev, y_dev, ctx->sf_xspec.p, ctx->fir8_ctr.p,
-                                 getenv("MSGPU_FIR8Q_MODE") ? atoi(getenv("MSGPU_FIR8Q_MODE")) : 0));
+                                 ctx->sf_hspec.p, x_dev, y_dev, ctx->sf_xspec.p, ctx->fir8_ctr.p));
         HIPCHK(ctx, done.finish());
         return MSG_OK;
     }
@@ -1128,7 +1059,7 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
             const unsigned grid = (unsigned)std::max(MSG_XCDS, (std::min(nj, ctx->n_cu) / MSG_XCDS) * MSG_XCDS);
             HIPCHK(ctx, fir8_counters(ctx, s));
             HIPCHK(ctx, launch_fir8p((unsigned)nj, grid, s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab,
-                                     ctx->sf_hspec.p, x_dev, y_dev, ctx->fir8_ctr.p, 0, nullptr, nullptr, nullptr));
+                                     ctx->sf_hspec.p, x_dev, y_dev, ctx->fir8_ctr.p, nullptr, nullptr, nullptr));
         } else {
             HIPCHK(ctx, launch_fir8((unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab,
                                     ctx->sf_hspec.p, x_dev, y_dev));
@@ -1445,12 +1376,7 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
                     keybuf[m++] = ((uint64_t)(uint32_t)off[k] << 32) | (uint32_t)k;
                     omax = std::max(omax, (uint32_t)off[k]);
                 }
-#if MSG_TAP_RADIX
             const uint64_t* key = sort_taps_by_offset(keybuf.data(), tmpbuf.data(), m, omax);
-#else                                                    // tuning A/B: the comparison sort
-            std::sort(keybuf.begin(), keybuf.begin() + m);
-            const uint64_t* key = keybuf.data();
-#endif
             int live = 0;
             if (dev_gain) {                              // slots -> key ranges, summed by k_er_gains
                 int32_t* kx = ctx->h_er_key.data() + tap_base[p];
@@ -1548,7 +1474,7 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     const bool stop_cep = stop_env && std::strcmp(stop_env, "cep") == 0;
     std::vector<int32_t> spec3;                           // events of the band-pruned kernel
     std::vector<int32_t> f32_presets;                     // presets on the float32 chain
-    std::vector<int2> fjobs_by[7];                        // FIR output blocks per transform size; [5]: k_fir4s, [6]: k_fir8
+    std::vector<int2> fjobs_by[6];                        // FIR output blocks per transform size; [5]: k_fir8
     std::vector<int32_t> fir8_list;                       // ER presets on k_fir8 (N = 65536): k_fir8_hconv
     std::vector<int32_t> ir_only8;                        // IR-only presets on k_fir8: H = the IR's spectrum
     std::map<int, int64_t> ir8_spec_of;                   // IR index -> spectrum offset (before relocation)
@@ -1559,7 +1485,6 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     std::map<int, int64_t> ir4_spec_of;
     std::vector<int64_t> ir4_jobs;
     int64_t ir4_sum = 0;
-    std::vector<int2> fir4s_presets;                      // (preset, blocks) on the streaming FIR
     // float64 grain chain records
     std::vector<Ev64> ev64;
     std::vector<int32_t> gen64_list;                      // normal-driven float64 events (event slots)
@@ -1596,32 +1521,15 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
         if (full8) return std::min<int64_t>(span, std::max<int64_t>(0, info[p].out_n - 1)) + irl;
         return std::max<int64_t>(1, std::min<int64_t>(span + irl, info[p].out_n));
     };
-    // k_fir4s pays one extra forward transform per workgroup: it is offered only
-    // when the batch's streaming-eligible blocks give >= 2 blocks per workgroup
-    bool fir4s_ok = false;
-    int fir4s_k = 1;                                      // blocks per k_fir4s workgroup
-    if (ctx->fir4 && ctx->fir4s) {
-        int64_t total = 0;
-        for (int p = 0; p < P; ++p) {
-            const int64_t M = h_taps(p);
-            if (M > 0 && M <= 2 * FIR4S_P)
-                total += (info[p].out_n + FIR4S_P - 1) / FIR4S_P;
-        }
-        fir4s_k = (int)std::min<int64_t>(ctx->fir4s_kmax, total / std::max(1, ctx->fir4s_wgs));
-        fir4s_ok = fir4s_k >= 2;
-    }
     // the per-preset pure functions of the records (FIR partitioning, stereo
     // Bessel taps) in parallel; the loop below does the prefix bookkeeping
-    struct FirPick { int64_t M; int N, P, Q; bool stream; float bess[25]; };
+    struct FirPick { int64_t M; int N, P, Q; float bess[25]; };
     std::vector<FirPick> pick(P);
     HostPool::get().run(P, [&](int p) {
         FirPick& f = pick[p];
         f.M = h_taps(p);
         f.N = f.P = f.Q = 0;
-        f.stream = false;
-        if (f.M > 0)
-            choose_fir(f.M, info[p].out_n, f.N, f.P, f.Q, ctx->fir8, fir4s_ok ? &f.stream : nullptr, fir4s_k,
-                       h_taps(p, true));
+        if (f.M > 0) choose_fir(f.M, info[p].out_n, f.N, f.P, f.Q, ctx->fir8, h_taps(p, true));
         const double w = std::min(std::max(presets[p].stereo_width, 0.0), 1.0);
         for (int m = 0; m <= 12; ++m) {                // J_{-m} = (-1)^m J_m: one series per |m|
             const double j = bessel_j(m, w * 0.9);
@@ -1638,7 +1546,7 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     if (ctx->ola_fir && ctx->fir8p > 0) {
         double grains = 0.0, frames = 0.0;
         for (int p = 0; p < P; ++p)
-            if (pick[p].M > 0 && pick[p].N == FIR8_N && !pick[p].stream) {
+            if (pick[p].M > 0 && pick[p].N == FIR8_N) {
                 grains += (double)info[p].pool_len;
                 frames += (double)info[p].out_n;
             }
@@ -1704,7 +1612,6 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
         if (r.fir_on) {
             const int64_t M = pick[p].M;
             const int N = pick[p].N, Pp = pick[p].P, Q = pick[p].Q;
-            const bool stream = pick[p].stream;
             if (N != FIR8_N) {                     // runtime plan for k_fir_h (k_fir8 has its own engine)
                 std::string why;
                 const int fp = real_plan(ctx->fir_plans, N, why);
@@ -1712,7 +1619,7 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
                 fir_plan_of[p] = fp;
                 fir_lds = std::max(fir_lds, ctx->fir_plans.host[fp].lds_bytes);
             }
-            r.fir_N = N; r.fir_P = Pp; r.fir_Q = Q; r.fir_B = stream ? Pp : N - Pp + 1;
+            r.fir_N = N; r.fir_P = Pp; r.fir_Q = Q; r.fir_B = N - Pp + 1;
             r.h_off = hsum;
             r.h_len = (int32_t)M;
             h_tile_begin[p] = htiles;
@@ -1772,17 +1679,13 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
             const int32_t nblk = (int32_t)((inf.out_n + r.fir_B - 1) / r.fir_B);
             // the overlap-add in k_fir8p's segment loads: each segment sums its grains
             // again (N / B ~ 1.6 times per frame), worth it while the grains are sparse
-            if (N == FIR8_N && !stream && batch_ola) {
+            if (N == FIR8_N && batch_ola) {
                 r.ola_fir = 1;
                 n_ola_fir++;
                 ola_fir_nmax = std::max<int64_t>(ola_fir_nmax, inf.out_n);
             }
-            if (stream) {
-                fir4s_presets.push_back(make_int2(p, nblk));   // jobs cut once the batch's total is known
-            } else {
-                std::vector<int2>& fj = fjobs_by[N == FIR8_N ? 6 : __builtin_ctz(N) - 11];
-                for (int32_t b = 0; b < nblk; ++b) fj.push_back(make_int2(p, b));
-            }
+            std::vector<int2>& fj = fjobs_by[N == FIR8_N ? 5 : __builtin_ctz(N) - 11];
+            for (int32_t b = 0; b < nblk; ++b) fj.push_back(make_int2(p, b));
             fblocks += nblk;
             hblocks += Q;
             if (!r.h_fir4) hblocks_gen += Q;
@@ -2039,22 +1942,19 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     HIPCHK(ctx, ctx->state64.ensure(state_sum));
     HIPCHK(ctx, ctx->so_r2.ensure(r2_sum));
     HIPCHK(ctx, ctx->so_A.ensure(so_M));
-    // k_fir4s: each workgroup walks fir4s_k consecutive blocks of one preset
-    for (const int2& pb : fir4s_presets)
-        for (int32_t b = 0; b < pb.y; b += fir4s_k) fjobs_by[5].push_back(make_int2(pb.x, b));
     std::vector<int2> fir_jobs;
-    int32_t fjob_off[8] = {0};
-    for (int i = 0; i < 7; ++i) {
+    int32_t fjob_off[7] = {0};
+    for (int i = 0; i < 6; ++i) {
         fjob_off[i] = (int32_t)fir_jobs.size();
         fir_jobs.insert(fir_jobs.end(), fjobs_by[i].begin(), fjobs_by[i].end());
     }
-    fjob_off[7] = (int32_t)fir_jobs.size();
+    fjob_off[6] = (int32_t)fir_jobs.size();
     // the fused overlap-add's first event per k_fir8p block: the events of a
     // preset are sorted by start, so one moving index per preset finds, block by
     // block, the first event starting after the segment's start - max_n
     std::vector<int32_t> fir_lo;
     if (n_ola_fir > 0) {
-        const std::vector<int2>& fj = fjobs_by[6];
+        const std::vector<int2>& fj = fjobs_by[5];
         fir_lo.resize(fj.size());
         int cur_p = -1, k = 0;
         for (size_t j = 0; j < fj.size(); ++j) {
@@ -2218,24 +2118,20 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     // ---- generate ----
     stage_mark(ctx, 2, s);
     if (!gen_list.empty())
-        hipLaunchKernelGGL(k_gen_normal<false>, dim3((unsigned)gen_list.size()), dim3(GEN_T * GEN_K), 0, s,
+        hipLaunchKernelGGL(k_gen_normal<false>, dim3((unsigned)gen_list.size()), dim3(GEN_T), 0, s,
                            ctx->presets.p, ctx->events.p, ctx->prt.p, ctx->gen_list.p, (int)gen_list.size(),
                            ctx->dzig, ctx->d_jump, ctx->micro.p, (double*)nullptr, (const int64_t*)nullptr);
     HIPCHK(ctx, hipGetLastError());
     if (!gen64_list.empty())   // raw normals of the float64 chain's normal-driven generators
-        hipLaunchKernelGGL(k_gen_normal<true>, dim3((unsigned)gen64_list.size()), dim3(GEN_T * GEN_K), 0, s,
+        hipLaunchKernelGGL(k_gen_normal<true>, dim3((unsigned)gen64_list.size()), dim3(GEN_T), 0, s,
                            ctx->presets.p, ctx->events.p, ctx->prt.p, ctx->gen64_list.p, (int)gen64_list.size(),
                            ctx->dzig, ctx->d_jump, ctx->micro.p, ctx->micro64.p, (const int64_t*)ctx->gen64_off.p);
     HIPCHK(ctx, hipGetLastError());
     // ---- spectral chain ----
     stage_mark(ctx, 3, s);
-    if (!spec3.empty()) {
-        if (ctx->spec3p > 0) HIPCHK(ctx, spec3_counters(ctx, s));
+    if (!spec3.empty())
         HIPCHK(ctx, launch_spec3((unsigned)spec3.size(), s, ctx->events.p, ctx->ert.p, ctx->prt.p, ctx->d_spec3_tab,
-                                 ctx->spec3_list.p, (int)spec3.size(), ctx->micro.p, ctx->grain.p,
-                                 ctx->spec3p > 1 ? ctx->spec3p : (ctx->spec3p > 0 ? ctx->n_cu : 0),
-                                 ctx->spec3_ctr.p));
-    }
+                                 ctx->spec3_list.p, (int)spec3.size(), ctx->micro.p, ctx->grain.p));
     for (int i = 0; i < SPEC_CT_PLANS; ++i)
         if (ct_off[i + 1] > ct_off[i])
             HIPCHK(ctx, launch_spectral_ct(i, (unsigned)(ct_off[i + 1] - ct_off[i]), s, ctx->events.p, ctx->ert.p,
@@ -2281,10 +2177,10 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
         if (!h_early)
             if (const int rc = launch_h_spectra()) return rc;
         stage_mark(ctx, 8, s);
-        for (int i = 0; i < 7; ++i) {
+        for (int i = 0; i < 6; ++i) {
             if (fjob_off[i + 1] <= fjob_off[i]) continue;
             const unsigned nj = (unsigned)(fjob_off[i + 1] - fjob_off[i]);
-            if (i == 6 && ctx->fir8p > 0) {
+            if (i == 5 && ctx->fir8p > 0) {
                 // persistent: one workgroup per CU (at most one per block), a multiple of the XCD
                 // count.  Long outputs (h_early: milliseconds per launch) leave one CU in eight
                 // to the other streams' small kernels, which cannot start beside a k_fir8p
@@ -2296,14 +2192,10 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
                 HIPCHK(ctx, fir8_counters(ctx, s));
                 HIPCHK(ctx, launch_fir8p(nj, grid, s, ctx->prt.p, ctx->fir_jobs.p + fjob_off[i],
                                          ctx->d_fir4tab, ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p, ctx->fir8_ctr.p,
-                                         ctx->fir8p_stagger,
                                          n_ola_fir > 0 ? ctx->events.p : nullptr, ctx->grain.p, ctx->fir_lo.p));
-            } else if (i == 6)
+            } else if (i == 5)
                 HIPCHK(ctx, launch_fir8(nj, s, ctx->prt.p, ctx->fir_jobs.p + fjob_off[i], ctx->d_fir4tab, ctx->hspec.p,
                                         ctx->mono_a.p, ctx->mono_y.p));
-            else if (i == 5)
-                HIPCHK(ctx, launch_fir4s(16384, nj, s, ctx->prt.p, ctx->fir_jobs.p + fjob_off[i], ctx->d_fir4tab,
-                                         ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p, fir4s_k));
             else if (i == 4 && ctx->fir4)
                 HIPCHK(ctx, launch_fir4(16384, nj, s, ctx->prt.p, ctx->fir_jobs.p + fjob_off[i], ctx->d_fir4tab,
                                         ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p));
@@ -2321,33 +2213,15 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     }
     // ---- stereo, tanh, normalise ----
     stage_mark(ctx, 6, s);
-    // peak of L (and the float64 FIR's error predictor) over the float32 y; the
-    // fused launch also writes the output of every preset it does not defer
-    // (float64 FIR slots, odd lengths: k_stereo_out_list below)
+    // peak of L (and the float64 FIR's error predictor) over the float32 y
     StereoSync sy{};
-    HIPCHK(ctx, ensure_zeroed(ctx->st_done, P, s));
-    HIPCHK(ctx, ensure_zeroed(ctx->st_ready, P, s));
-    sy.done = ctx->st_done.p;
-    sy.ready = ctx->st_ready.p;
     sy.flag64 = f64_on ? ctx->f64_flag.p : nullptr;
     sy.part = f64_on ? ctx->st_part.p : nullptr;
     sy.stats = f64_on ? ctx->f64_stats.p : nullptr;
-    ctx->st_epoch = ctx->st_epoch % ((1u << 30) - 1) + 1;
-    sy.epoch = ctx->st_epoch;
     sy.f64mode = f64_on ? ctx->fir64 : 0;
-    int st_tmax = 0;
-    for (int p = 0; p < P; ++p) st_tmax = std::max(st_tmax, st_count[p]);
-    const bool st_fused = ctx->stereo_fused && st_tmax <= ST_FUSED_MAX_TILES;
-    if (st_fused) {
-        if (!ctx->st_ctr.p) HIPCHK(ctx, ensure_zeroed(ctx->st_ctr, ST_CTR_N, s));   // every launch leaves them zero
-        const unsigned grid = (unsigned)std::max(1, std::min(stiles, ctx->n_cu * ctx->st_wgs));
-        HIPCHK(ctx, launch_stereo_fused(grid, (unsigned)stiles, s, ctx->prt.p, ctx->st_begin.p, P, yb, ctx->maxbits.p,
-                                        sy, ctx->st_ctr.p, out_dev));
-    } else {
-        HIPCHK(ctx, launch_stereo_max((unsigned)stiles, s, ctx->prt.p, ctx->st_begin.p, P, yb, ctx->maxbits.p, sy));
-        if (f64_on)   // the float64 FIR's predictor per preset, from the tiles' partial sums
-            HIPCHK(ctx, launch_stereo_pred((unsigned)P, s, ctx->prt.p, ctx->st_begin.p, stiles, ctx->maxbits.p, sy));
-    }
+    HIPCHK(ctx, launch_stereo_max((unsigned)stiles, s, ctx->prt.p, ctx->st_begin.p, P, yb, ctx->maxbits.p, sy));
+    if (f64_on)   // the float64 FIR's predictor per preset, from the tiles' partial sums
+        HIPCHK(ctx, launch_stereo_pred((unsigned)P, s, ctx->prt.p, ctx->st_begin.p, stiles, ctx->maxbits.p, sy));
     if (f64_on) {   // flagged presets: the FIR again in float64, y overwritten (kernels_fir64.h)
         Fir64Launch a;
         a.rt = ctx->prt.p; a.n_presets = P; a.flag64 = ctx->f64_flag.p; a.maxbits = ctx->maxbits.p;
@@ -2412,19 +2286,8 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
         HIPCHK(ctx, launch_stereo_remax((unsigned)std::min<int64_t>((int64_t)n_odd * odd_tmax, 4096), s, ctx->prt.p,
                                         ctx->st_count.p, ctx->odd_list.p, ctx->odd_cnt.p, odd_tmax, yb, ctx->so_r2.p,
                                         ctx->maxbits.p));
-    if (st_fused) {   // the deferred presets' output
-        if (f64_on)
-            HIPCHK(ctx, launch_stereo_out_list((unsigned)std::min<int64_t>((int64_t)f64_cand * f64_stmax, 1024), s, ctx->prt.p,
-                                               ctx->st_count.p, ctx->f64_slot_preset.p, ctx->f64_nslots.p, f64_stmax,
-                                               yb, ctx->so_r2.p, ctx->maxbits.p, out_dev));
-        if (n_odd > 0)
-            HIPCHK(ctx, launch_stereo_out_list((unsigned)std::min<int64_t>((int64_t)n_odd * odd_tmax, 4096), s,
-                                               ctx->prt.p, ctx->st_count.p, ctx->odd_list.p, ctx->odd_cnt.p, odd_tmax,
-                                               yb, ctx->so_r2.p, ctx->maxbits.p, out_dev));
-    } else {
-        HIPCHK(ctx, launch_stereo_out((unsigned)stiles, s, ctx->prt.p, ctx->st_begin.p, P, yb, ctx->so_r2.p,
-                                      ctx->maxbits.p, out_dev));
-    }
+    HIPCHK(ctx, launch_stereo_out((unsigned)stiles, s, ctx->prt.p, ctx->st_begin.p, P, yb, ctx->so_r2.p,
+                                  ctx->maxbits.p, out_dev));
     stage_mark(ctx, 7, s);
     HIPCHK(ctx, done.finish());
     ctx->h_info = info;

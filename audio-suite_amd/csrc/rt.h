@@ -131,21 +131,13 @@ struct Fir64Rt {
     int32_t st_tiles;              // stereo tiles (k_stereo_remax)
 };
 
-// Cross-workgroup state of the max pass (per context, reused launch to launch).
+// The max pass's hand-over to k_stereo_pred (per context, reused launch to launch).
 struct StereoSync {
-    int32_t* done;       // per preset: max-pass tiles finished (the preset's last tile resets it to 0)
-    uint32_t* ready;     // per preset: (epoch << 1) | deferred once every max-pass tile is done
     int32_t* flag64;     // per preset: 1 = takes the float64 FIR (null when the route is off)
     double* part;        // per stereo tile: the tile's sum y^2, sum q^2 (null when the route is off)
     double* stats;       // per preset: the same sums over the preset, added in tile order
-    uint32_t epoch;      // this launch's tag, 1 .. 2^30
     int f64mode;         // 0 route off, 1 predicted, 2 every FIR preset (MSGPU_FIR64)
 };
-constexpr int ST_CTR_A = 0, ST_CTR_E = 32, ST_CTR_N = 64;   // k_stereo_fused counters, 128 B apart
-// the fused stereo launch takes batches whose presets have at most this many
-// stereo tiles (kernels_stereo.h: its deadlock-freedom bound); longer ones run
-// k_stereo_max + k_stereo_out
-constexpr int ST_FUSED_MAX_TILES = 2048;
 
 constexpr int GEN_T = 64;          // one wave per event
 constexpr int OLA_T = 256;
@@ -166,7 +158,6 @@ constexpr int ST_TILE = MSG_ST_TILE;
 // takes one contiguous range of jobs: the shared lines then stay in one L2.
 constexpr int MSG_XCDS = 8;
 constexpr int FIR8P_CTR = 32;   // int32 stride of k_fir8p's per-XCD block counters (128 B apart)
-constexpr int S3P_CTR = 32;     // int32 stride of k_spec3p's per-XCD event counters (128 B apart)
 __device__ __forceinline__ int xcd_block(int b, int grid) {
     const int x = b % MSG_XCDS, i = b / MSG_XCDS;
     const int per = grid / MSG_XCDS, rem = grid % MSG_XCDS;

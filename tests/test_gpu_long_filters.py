@@ -278,24 +278,6 @@ def test_fir8_persistent_bit_identical(msgpu, irs, full_renders):
     assert rms(outs["1"][:int(packed.out_n[0])], full_renders["C3_audio"]) <= RMS_TOL
 
 
-def test_spec3_persistent_bit_identical(msgpu, irs, full_renders):
-    """k_spec3's persistent form (MSGPU_SPEC3P=1: one workgroup per CU taking
-    events from per-XCD counters, each next grain loaded during the current
-    event) runs every event with the two-event chain's arithmetic (=0): the
-    outputs are bit-identical on C3 (narrow band), C4 (wide band), a batch of
-    fewer events than CUs and one whose event count is not a multiple of the
-    XCD count; C3 still matches the reference render."""
-    params = [msgpu.config_params("C3", seed=1000 + s, irs=irs) for s in range(3)]
-    params += [msgpu.config_params("C4", seed=1000, irs=irs), msgpu.merged(out_dur_s=0.2, seed=5)]
-    outs = {m: _render_env(params, {"MSGPU_SPEC3P": m})[1] for m in ("0", "1")}
-    assert np.array_equal(outs["0"], outs["1"])
-    few = [msgpu.config_params("C3", seed=3000, irs=irs, out_dur_s=0.2)]      # a handful of events
-    fo = {m: _render_env(few, {"MSGPU_SPEC3P": m})[1] for m in ("0", "1")}
-    assert np.array_equal(fo["0"], fo["1"])
-    packed, _ = _render_env(params[:1], {})
-    assert rms(outs["1"][:int(packed.out_n[0])], full_renders["C3_audio"]) <= RMS_TOL
-
-
 def test_fir64_serves_every_flagged_preset(msgpu, irs):
     """the float64 FIR had 128 slots per batch and left flagged
     presets beyond them on float32, so a preset's output depended on the batch
@@ -343,24 +325,21 @@ def test_fir64_windows_bit_identical(msgpu, irs):
             assert np.array_equal(many[off:off + nq], oneq[:nq]), i
 
 
-def test_stereo_fused_matches_two_launches(msgpu, irs):
-    """k_stereo_fused (MSGPU_STEREO_FUSED=1: max and output passes in one
-    persistent launch, deferred float64-FIR and odd-length presets) writes the
-    same bits as k_stereo_max + k_stereo_out, and the float64 FIR's per-preset
-    sums are added in tile order, so two renders are identical."""
+def test_mixed_batch_renders_identically_twice(msgpu, irs):
+    """A batch that mixes float32-FIR, float64-FIR, unfiltered, odd-length and
+    C2 presets: the float64 FIR's per-preset sums are added in tile order
+    (ADVICE r04), so two renders are identical."""
     base = dict(gen_mode="Resonant strike", event_process="Poisson", _ir_audio=irs["tiny_room_ir"])
     params = [msgpu.config_params("C3", seed=1000 + s, irs=irs, out_dur_s=0.3) for s in range(3)]
     params += [msgpu.merged(base, base_sr=48000, out_dur_s=0.3, space_ir_on=True, seed=22, er_cloud_on=True,
-                            space_ir_max_samps=8192, stereo_width=0.3),          # float64 FIR (deferred)
+                            space_ir_max_samps=8192, stereo_width=0.3),          # float64 FIR
                msgpu.merged(out_dur_s=0.2, seed=5),                             # no filter
-               msgpu.merged(out_dur_s=0.2000208, seed=6, base_sr=48000),        # odd length (deferred)
+               msgpu.merged(out_dur_s=0.2000208, seed=6, base_sr=48000),        # odd length
                msgpu.config_params("C2", seed=1000, irs=irs, out_dur_s=0.25)]
-    _, two = _render_env(params, {"MSGPU_STEREO_FUSED": "0"})
-    _, two_again = _render_env(params, {"MSGPU_STEREO_FUSED": "0"})
-    packed, fused = _render_env(params, {"MSGPU_STEREO_FUSED": "1"})
+    packed, two = _render_env(params, {})
+    _, two_again = _render_env(params, {})
     assert int(packed.out_n[5]) % 2 == 1
     assert np.array_equal(two, two_again)
-    assert np.array_equal(two, fused)
 
 
 def test_fir4_spectra_from_taps(msgpu, irs):

@@ -2,7 +2,7 @@
 # GPU box: the round-6 A/B and diagnostic sessions, one function each (their
 # records are under profiles/r06*; DESIGN section 9 cites them).
 #   usage (on the box): bash tools/round6_ab.sh NAME [args]
-# NAME: c3_streams c3_streams32 h48_host_diag h48_numa_diag h48_sched gate_points_ab gate_c3_ab h48_streams_ab prof_every_ab prof_every_ab2 h48_warmup_ab sub_sweep s3p_check fir8_cus_stamps ho_check q2nt_ab mb_check c5_sub_ab q2_ahead1_ab
+# NAME: c3_streams c3_streams32 h48_host_diag h48_numa_diag h48_sched gate_points_ab gate_c3_ab h48_streams_ab prof_every_ab prof_every_ab2 h48_warmup_ab sub_sweep fir8_cus_stamps ho_check q2nt_ab mb_check c5_sub_ab
 set -o pipefail
 O=${MSGPU_OUT:-bench_out}; mkdir -p "$O"
 
@@ -201,20 +201,6 @@ for i in 1 2; do
 done
 }
 
-# GPU box: k_spec3p (MSGPU_SPEC3P=1) against the two-event chain -- bits on the
-# mixed batch and on C3 / C4, the spectral tests under the persistent form,
-# then the isolated / timed A/B on C3 and C4.
-s3p_check() {
-L=audio-suite_amd/msgpu/libmsgpu.so
-timeout -k 10 300 python tools/bits_ab.py "$L,MSGPU_SPEC3P=0" "$L,MSGPU_SPEC3P=1" > $O/r06u_bits.json 2> $O/r06u_bits.log
-echo "bits rc=$?"; cat $O/r06u_bits.json
-timeout -k 10 400 python -u -m pytest tests/test_gpu_long_filters.py -k 'spec3_persistent or fir8_persistent' -m gpu -x -q -s --timeout 200 --timeout-method thread > $O/r06u_tests0.txt 2>&1; echo "persist test rc=$?"; tail -3 $O/r06u_tests0.txt
-MSGPU_SPEC3P=1 timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -k 'spec3 or C3 or C4' -m gpu -x -q --timeout 200 --timeout-method thread > $O/r06u_tests.txt 2>&1
-rc=$?; echo "tests rc=$rc"; tail -3 $O/r06u_tests.txt
-[ $rc -gt 1 ] && exit $rc
-bash tools/ab_env.sh r06u 'p0|MSGPU_SPEC3P=0|base' 'p1|MSGPU_SPEC3P=1|base' 'p0b|MSGPU_SPEC3P=0|base' 'p1b|MSGPU_SPEC3P=1|base'
-}
-
 # GPU box: k_fir8p phase stamps against the number of persistent workgroups
 # (MSGPU_FIR8P_CUS): does a block's segment-load phase shrink when fewer CUs
 # share HBM (bandwidth share) or stay (latency)?
@@ -300,19 +286,6 @@ for i in ${C5_REPS:-1 2}; do
     python3 -c "
 import json; d=json.load(open('$O/r06c5s_${sub}_$i.json'))
 print('C5 sub $sub', $i, d['ms_per_step'], d['checked']['all_ok'], d['config'].get('sub_batches_per_gpu'), d['config'].get('stream_gate'))"
-  done
-done
-}
-
-# k_fir8q with the carry loaded one pair ahead (libmsgpu_a1.so, MSG_Q2_AHEAD=1) vs product, FIR points, alternating
-q2_ahead1_ab() {
-L=$PWD/audio-suite_amd/msgpu
-for rep in 1 2 3; do
-  for lib in base a1; do
-    if [ $lib = base ]; then le=""; else le="MSGPU_LIB=$L/libmsgpu_$lib.so"; fi
-    env $le timeout -k 10 300 python bench.py --full --no-cpu --points= --steps 5 --from-dicts-steps 0 --iso-steps 0 > $O/r06a1_$lib$rep.json 2>/dev/null || exit $?
-    python3 -c "
-import json; d=json.load(open('$O/r06a1_$lib$rep.json')); print('$lib$rep', {k: (v['ms_per_step'], v['roofline']['frac'], v['check']['all_ok']) for k, v in d['points'].items() if k.startswith('FIR')})"
   done
 done
 }
