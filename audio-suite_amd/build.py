@@ -32,7 +32,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "msgpu", "libmsgpu.so")
 TUS = ["msgpu.hip", "k_spectral.hip", "k_spectral_ct.hip", "k_spec3.hip", "k_fir.hip", "k_grain64.hip", "k_grain64_lds.hip",
-       "k_grain64_glb.hip", "k_stereo_odd.hip", "k_fir64.hip", "k_stereo.hip", "k_digest.hip"]
+       "k_grain64_glb.hip", "k_stereo_odd.hip", "k_fir64.hip", "k_stereo.hip", "k_digest.hip", "k_resample.hip"]
 HEADERS = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
           [os.path.join(os.path.dirname(HERE), "include", "msgpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -42,7 +42,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 # records (msgpu.hip): SSE4.1 turns rint / nearbyint into one roundsd instead of
 # a libm call (plan_sizes 0.63 -> 0.43 us, plan_events 2.9 -> 2.2 us per H48
 # preset on this container); no FMA, so host float results keep their bits
-TU_HOST_FLAGS = {"msgpu.hip": ["-Xarch_host", "-msse4.1"]}
+TU_HOST_FLAGS = {"msgpu.hip": ["-Xarch_host", "-msse4.1"],
+                 # the resampler's FIR loops slide a register window along 16-byte LDS reads; the
+                 # SLP vectoriser turns their FMAs into packed ones fed by twice as many moves
+                 # (27 VALU instructions per 16 FMAs against 20), so it is off for this TU
+                 "k_resample.hip": ["-fno-slp-vectorize"]}
 
 
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)

@@ -70,6 +70,10 @@ int msg_stft_mag_db(msg_ctx*, const void*, int32_t, int64_t, int32_t, int32_t, i
 int msg_digest(msg_ctx*, const float*, const int64_t*, const int64_t*, int32_t, msg_digest_rec*, void*) {
     return no_device();
 }
+int msg_resample(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, const double*,
+                 int64_t, float*, const int64_t*, void*) {
+    return no_device();
+}
 // the digest's host reference (digest.h), the same code the product library runs
 int msg_digest_host(const float* x, int64_t out_n, msg_digest_rec* rec) {
     if (!rec || out_n < 0 || (out_n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");

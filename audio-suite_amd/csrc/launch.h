@@ -6,6 +6,7 @@
 #include <vector>
 #include "rt.h"
 #include "fft64.h"
+#include "resample.h"
 
 constexpr int LDS_MAX = 163840;                              // 160 KiB per CU
 constexpr int SPEC_T_BIG = 512, SPEC_M_BIG = 20480;           // up to 160 KiB LDS
@@ -179,3 +180,9 @@ hipError_t launch_digest(int n, int n_tiles, hipStream_t s, const float* out, co
                          const int64_t* frames, const int32_t* tile_base, void* part, void* res);
 int64_t digest_tiles(int64_t frames);
 void digest_host(const float* x, int64_t frames, void* rec);
+
+// polyphase resampler (kernels_resample.h): one workgroup per output tile of plan p;
+// meta holds four int64 rows of n_sig (input offsets, input frames, output offsets,
+// first tiles), tab the plan's tap table (rs_table)
+hipError_t launch_resample(const RsPlan& p, int channels, unsigned tiles, hipStream_t s, const float* x, float* y,
+                           const int64_t* meta, int n_sig, const float* tab, int up, int down, int64_t K);

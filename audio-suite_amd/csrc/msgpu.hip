@@ -295,6 +295,9 @@ struct msg_ctx {
     // msg_digest: render extents + tile bases, per-tile partials
     DevBuf<int64_t> dg_meta;
     DevBuf<char> dg_part;
+    // msg_resample: signal extents + tile bases, the tap table
+    DevBuf<int64_t> rs_meta;
+    DevBuf<float> rs_tab;
     // odd-length stereo rotation (kernels_stereo_odd.h)
     std::map<int64_t, DevBuf<double2>> so_bp;  // chirp kernel spectra by n (float64), LRU-bounded
     std::map<int64_t, uint64_t> so_bp_use;     // batch serial of each entry's last use
@@ -769,6 +772,7 @@ void msg_destroy(msg_ctx* ctx) {
     ctx->sf_prt.release(); ctx->sf_jobs.release(); ctx->sf_irjobs.release(); ctx->sf_h.release();
     ctx->sf_hspec.release(); ctx->sf_xspec.release(); ctx->sf_hf.release();
     ctx->dg_meta.release(); ctx->dg_part.release();
+    ctx->rs_meta.release(); ctx->rs_tab.release();
     for (auto& set : ctx->ev)
         for (auto& ev : set) hipEventDestroy(ev);
     {
@@ -1150,6 +1154,69 @@ int msg_digest(msg_ctx* ctx, const float* out_dev, const int64_t* out_offsets, c
     const int64_t* dm = ctx->dg_meta.p;
     HIPCHK(ctx, launch_digest(n_renders, (int)tiles, s, out_dev, dm, dm + n_renders,
                               reinterpret_cast<const int32_t*>(dm + 2 * (size_t)n_renders), ctx->dg_part.p, rec_dev));
+    HIPCHK(ctx, done.finish());
+    return MSG_OK;
+}
+
+int msg_resample(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* in_offsets, const int64_t* in_n,
+                 int32_t n_signals, int32_t up, int32_t down, const double* h, int64_t K, float* y_dev,
+                 const int64_t* out_offsets, void* stream) {
+    if (!ctx || !x_dev || !y_dev || !in_offsets || !in_n || !out_offsets || n_signals < 0)
+        return fail(ctx, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
+    if (up < 1 || down < 1) return fail(ctx, MSG_E_VALUE, "the ratio must be positive");
+    if (up != down && (!h || K < 1 || (K & 1) == 0)) return fail(ctx, MSG_E_VALUE, "the tap count must be odd");
+    if (up > RS_RATIO_MAX || down > RS_RATIO_MAX)
+        return fail(ctx, MSG_E_UNSUPPORTED, "ratio beyond the resampler's limits");
+    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
+        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    RsPlan plan{};
+    if (up != down) {
+        plan = rs_plan(up, down, K, channels);
+        if (plan.kind < 0) return fail(ctx, MSG_E_UNSUPPORTED, "ratio beyond the resampler's tap-table or LDS limit");
+    }
+    // rows: input offsets, input frames, output offsets, first tiles
+    std::vector<int64_t> meta((size_t)4 * n_signals);
+    int64_t tiles = 0, x_end = 0, y_end = 0;
+    for (int i = 0; i < n_signals; ++i) {
+        if (in_n[i] < 0 || in_n[i] > MSG_MAX_FRAMES || in_offsets[i] < 0 || out_offsets[i] < 0)
+            return fail(ctx, MSG_E_ARG, "bad signal extent");
+        const int64_t n_out = rs_out_len(in_n[i], up, down);
+        if (n_out > MSG_MAX_FRAMES) return fail(ctx, MSG_E_UNSUPPORTED, "output longer than 2^31 - 2^20 frames");
+        meta[i] = in_offsets[i];
+        meta[(size_t)n_signals + i] = in_n[i];
+        meta[(size_t)2 * n_signals + i] = out_offsets[i];
+        meta[(size_t)3 * n_signals + i] = tiles;
+        if (up != down) tiles += (n_out + plan.tile - 1) / plan.tile;
+        x_end = std::max(x_end, in_offsets[i] + in_n[i]);
+        y_end = std::max(y_end, out_offsets[i] + n_out);
+    }
+    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many output tiles");
+    if (x_dev < y_dev + y_end * channels && y_dev < x_dev + x_end * channels)
+        return fail(ctx, MSG_E_ARG, "x and y must not alias");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, stream_handover(ctx, s));
+    DoneGuard done(ctx, s);
+    if (up == down) {                                       // a copy
+        for (int i = 0; i < n_signals; ++i)
+            if (in_n[i] > 0)
+                HIPCHK(ctx, hipMemcpyAsync(y_dev + out_offsets[i] * channels, x_dev + in_offsets[i] * channels,
+                                           sizeof(float) * (size_t)(in_n[i] * channels), hipMemcpyDeviceToDevice, s));
+        HIPCHK(ctx, done.finish());
+        return MSG_OK;
+    }
+    if (tiles == 0) { HIPCHK(ctx, done.finish()); return MSG_OK; }
+    std::vector<float> tab((size_t)plan.tab);
+    rs_table(plan, up, down, h, K, tab.data());
+    HIPCHK(ctx, ctx->rs_meta.ensure(meta.size()));
+    HIPCHK(ctx, ctx->rs_tab.ensure(tab.size()));
+    // pageable sources are staged before hipMemcpyAsync returns (as msg_fir's uploads)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rs_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rs_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, launch_resample(plan, channels, (unsigned)tiles, s, x_dev, y_dev, ctx->rs_meta.p, n_signals,
+                                ctx->rs_tab.p, up, down, K));
     HIPCHK(ctx, done.finish());
     return MSG_OK;
 }

@@ -9,6 +9,10 @@ The compute path is libmsgpu.so (HIP kernels for gfx950) bound by ctypes; there
 is no CPU fallback.
 """
 from .params import DEFAULTS, CONFIGS, config_params, merged  # noqa: F401
+# the submodule first: importing it later would rebind the name ``msgpu.resample``
+# from the function below to the module (reach the module's names with
+# ``from msgpu.resample import design, ...``)
+from . import resample as _resample  # noqa: F401
 
 
 def render(params, progress=None, device: int = 0):
@@ -16,19 +20,26 @@ def render(params, progress=None, device: int = 0):
     return _render(params, progress, device)
 
 
-def render_batch(params_list, device: int = 0, devices=None, results: str = "audio"):
+def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
     preset, multi.audio_stats) or "device" (the renders stay in HBM: device
-    tensors on one GPU, multi.DeviceResult handles across several)."""
+    tensors on one GPU, multi.DeviceResult handles across several).
+    ``out_sr``: deliver "audio" / "device" results at that rate, resampled in HBM
+    before any copy (resample.py; one device only); ``out_peak``: None, "preset"
+    or a number, the peak each resampled render is rescaled to."""
     if devices is not None and len(list(devices)) > 1:
+        if out_sr is not None or out_peak is not None:
+            raise NotImplementedError("out_sr on more than one device (multi.py sizes its shared memory by out_n)")
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)
     if devices is not None:
         device = int(list(devices)[0])
     from .dropin import render_batch as _rb
-    return _rb(params_list, device, results)
+    if out_sr is None and out_peak is None:
+        return _rb(params_list, device, results)
+    return _rb(params_list, device, results, out_sr, out_peak)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):
@@ -57,8 +68,16 @@ def fir(x, h, device: int = 0):
     return y.cpu().numpy()
 
 
+def resample(x, sr_in, sr_out, device: int = 0, **design):
+    """Sample-rate conversion of x, (n,) or (n, 2), on the device (polyphase FIR,
+    Kaiser-windowed sinc; see resample.py).  NumPy in, float32 NumPy out; a device
+    tensor in, a device tensor out with no host synchronise."""
+    return _resample.resample(x, sr_in, sr_out, device, **design)
+
+
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0, devices=None, **kw):
     """The app's batch render (on_batch, MS:1524-1596); see batch.py.  ``devices``
-    shards the variants across GPUs as render_batch does."""
+    shards the variants across GPUs as render_batch does; ``export_sr`` /
+    ``export_peak`` deliver the variants at another sample rate (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

@@ -111,6 +111,9 @@ _PROTOS = {
     "msg_fft64": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "msg_fir": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                           C.POINTER(C.c_int32), C.c_void_p]),
+    "msg_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                               C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64),
+                               C.c_void_p]),
     "msg_stft_mag_db": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "msg_digest": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,

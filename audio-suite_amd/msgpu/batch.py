@@ -129,21 +129,35 @@ def _chunks(items, frames_of):
 
 
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0,
-                      names="wav", progress=None, devices=None):
+                      names="wav", progress=None, devices=None, export_sr=None, export_peak=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
     Returns a list of ``(name, audio, out_sr)`` in the reference's order (audio
     (out_n, 2) float32); with ``folder``, also writes each as a float32 WAV.
     ``progress(percent, text)`` gets the reference's status line per file.
+
+    ``export_sr``: deliver the variants at that rate instead of ``base_sr``: each
+    batch is resampled in HBM (resample.py) before it is copied to the host, and
+    the file names, WAV headers and the returned out_sr carry ``export_sr``.
+    ``export_peak="preset"`` rescales each resampled variant so that max|y| is the
+    preset's ``peak`` again (resampling moves the peak); None leaves the samples
+    as resampled.  One device only.
     """
     from .pack import PackedBatch, out_frames
 
+    if export_sr is None and export_peak is not None:
+        raise ValueError("export_peak needs export_sr")
+    if export_peak not in (None, "preset"):
+        raise ValueError("export_peak must be None or 'preset'")
+    if export_sr is not None and devices is not None and len(list(devices)) > 1:
+        raise NotImplementedError("export_sr on more than one device (multi.py sizes its shared memory by out_n)")
     base = merged(base_params)
     pairs = variants(base, seeds, unfolds, stretches)
     keys = [key for key, _ in pairs]
     total = max(1, len(keys))
-    out_sr = int(base["base_sr"])                 # every variant has the template's out_n and out_sr
+    base_sr = int(base["base_sr"])                # every variant has the template's out_n and base_sr
+    out_sr = base_sr if export_sr is None else int(export_sr)
     results = []
 
     def emit(key, audio):
@@ -167,8 +181,13 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     for chunk in _chunks(keys, lambda k: frames):
         packed = PackedBatch.variants(base, chunk)   # the template packed once (MS:1578-1584)
         out = eng.render_packed(packed)
+        offsets, lens = packed.offsets, packed.out_n
+        if export_sr is not None:                    # resampled where it lies; the copy below is the export-rate batch
+            from .dropin import resample_packed
+            peaks = [float(base["peak"])] * len(chunk) if export_peak == "preset" else None
+            out, offsets, lens = resample_packed(eng, out, offsets, lens, [base_sr] * len(chunk), out_sr, peaks)
         eng.torch.cuda.synchronize(eng.device)
         host = out.cpu().numpy()
-        for key, off, n in zip(chunk, packed.offsets, packed.out_n):
+        for key, off, n in zip(chunk, offsets, lens):
             emit(key, host[off:off + n].copy())
     return results

@@ -80,15 +80,84 @@ def _event_note(p, i):
     return ""
 
 
-def render_batch(params_list, device: int = 0, results: str = "audio"):
+def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
+    """Resample renders lying in a device output tensor ((frames, 2) float32, render i
+    at frame offsets[i] with lens[i] frames at sr_in[i] Hz) to out_sr where they lie
+    (msg_resample, one call per distinct input rate): returns (y, y_offsets, y_lens),
+    the outputs packed back to back in render order, enqueued on the current stream.
+    ``peaks`` (one per render, or None): rescale each resampled render so that
+    max|y| equals its peak, peak_normalize's rule (MS:26-29: a zero buffer stays
+    zero) -- resampling moves the peak.  Renders of one length are rescaled by one
+    reduction and one multiply over the batch."""
+    from .resample import design, ratio, resample_len
+    torch = eng.torch
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rates = [int(s) for s in sr_in]
+    ratios = [ratio(s, out_sr) for s in rates]
+    y_lens = np.array([resample_len(n, u, d) for n, (u, d) in zip(lens, ratios)], dtype=np.int64)
+    y_off = np.concatenate([[0], np.cumsum(y_lens)[:-1]]).astype(np.int64)
+    y = torch.empty((int(y_lens.sum()), 2), dtype=torch.float32, device=out.device)
+    for rate in sorted(set(rates)):
+        idx = [i for i, s in enumerate(rates) if s == rate]
+        up, down = ratio(rate, out_sr)
+        h = design(up, down) if up != down else None
+        if len(idx) == len(rates):            # one rate: the whole batch in one call
+            eng.resample(out, offsets, lens, 2, up, down, h, out=y)
+        else:                                 # mixed rates: Engine.resample packs a call's outputs back to back
+            for i in idx:
+                eng.resample(out, offsets[i:i + 1], lens[i:i + 1], 2, up, down, h, out=y[int(y_off[i]):])
+    if peaks is not None and len(y_lens):
+        pk = torch.tensor([float(p) for p in peaks], dtype=torch.float32, device=y.device)
+        if len(set(int(n) for n in y_lens)) == 1:
+            v = y.view(len(y_lens), -1)
+            m = v.abs().amax(dim=1)
+            v.mul_(torch.where(m > 0, pk / m, torch.ones_like(m)).unsqueeze(1))
+        else:
+            for i, (o, n) in enumerate(zip(y_off, y_lens)):
+                seg = y[int(o):int(o) + int(n)]
+                m = seg.abs().amax() if n else pk[i]
+                seg.mul_(torch.where(m > 0, pk[i] / m, torch.ones_like(m)))
+    return y, y_off, y_lens
+
+
+def _out_peaks(params_list, out_peak):
+    if out_peak is None:
+        return None
+    if isinstance(out_peak, str):
+        if out_peak != "preset":
+            raise ValueError("out_peak must be None, 'preset' or a number")
+        return [float(merged(p)["peak"]) for p in params_list]
+    return [float(out_peak)] * len(params_list)
+
+
+def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
-    reduced on the device by msg_digest) or the device tensors themselves ("device")."""
+    reduced on the device by msg_digest) or the device tensors themselves ("device").
+    ``out_sr``: deliver the renders at that rate, resampled in HBM before any copy
+    ("audio" or "device"); ``out_peak``: None, "preset" or a number, the peak the
+    resampled renders are rescaled to (resample_packed)."""
     if results not in ("audio", "stats", "device"):
         raise ValueError("results must be 'audio', 'stats' or 'device'")
+    if out_sr is None and out_peak is not None:
+        raise ValueError("out_peak needs out_sr")
+    if out_sr is not None and results == "stats":
+        raise ValueError("out_sr applies to results 'audio' or 'device'")
+    params_list = list(params_list)
     eng = default_engine(device)
-    packed = PackedBatch(list(params_list))
+    packed = PackedBatch(params_list)
     out = eng.render_packed(packed)
+    if out_sr is not None:
+        y, y_off, y_lens = resample_packed(eng, out, packed.offsets, packed.out_n,
+                                           [merged(p)["base_sr"] for p in params_list], int(out_sr),
+                                           _out_peaks(params_list, out_peak))
+        parts = [y[int(o):int(o) + int(n)] for o, n in zip(y_off, y_lens)]
+        if results == "device":
+            return parts
+        eng.torch.cuda.synchronize(eng.device)
+        host = y.cpu().numpy()
+        return [host[int(o):int(o) + int(n)].copy() for o, n in zip(y_off, y_lens)]
     if results == "device":
         return [out[int(o):int(o) + int(n)] for o, n in zip(packed.offsets, packed.out_n)]
     eng.torch.cuda.synchronize(eng.device)

@@ -145,6 +145,55 @@ class Engine:
                                     C.c_void_p(stream.cuda_stream)), self._ctx)
         return out, tuple(shape)
 
+    def resample(self, x, offsets, lens, channels, up, down, h, out=None, stream=None):
+        """msg_resample of signals lying in a device float32 tensor (mono samples or
+        interleaved L/R frames, signal i at frame offsets[i] with lens[i] frames):
+        each is resampled by up / down with the float64 taps h (resample.design;
+        None when up == down, a copy) and the outputs are packed back to back in
+        ``out`` (allocated when None; it must not alias x).  Returns (y, out_offsets,
+        out_lens), y of shape (frames,) or (frames, 2), enqueued on ``stream``."""
+        from .resample import resample_len
+        torch = self.torch
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device.type != "cuda":
+            raise ValueError("x must be a contiguous float32 device tensor")
+        channels = int(channels)
+        if channels not in (1, 2):
+            raise ValueError("channels must be 1 or 2")
+        up, down = int(up), int(down)
+        if up < 1 or down < 1:
+            raise ValueError("the ratio must be positive")
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        cnt = np.ascontiguousarray(lens, dtype=np.int64)
+        if off.shape != cnt.shape or off.ndim != 1:
+            raise ValueError("offsets and lens must be 1-D of one length")
+        if off.size and (int(off.min()) < 0 or int(cnt.min()) < 0 or
+                         int((off + cnt).max()) * channels > x.numel()):
+            raise ValueError("a signal extends past the input tensor")
+        out_cnt = np.array([resample_len(n, up, down) for n in cnt], dtype=np.int64)
+        out_off = np.concatenate([[0], np.cumsum(out_cnt)[:-1]]).astype(np.int64) if off.size else out_cnt
+        total = int(out_cnt.sum())
+        if out is None:
+            out = torch.empty((total,) if channels == 1 else (total, 2), dtype=torch.float32, device=x.device)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device or \
+                out.numel() < total * channels:
+            raise ValueError("out must be a contiguous float32 tensor on x's device with room for every output")
+        if up != down:
+            hh = np.ascontiguousarray(h, dtype=np.float64)
+            if hh.ndim != 1 or hh.size % 2 == 0:
+                raise ValueError("h must be 1-D with an odd number of taps")
+            hp, K = hh.ctypes.data_as(C.c_void_p), int(hh.size)
+        else:
+            hp, K = None, 0
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        with self._lock:
+            L.check(L.lib().msg_resample(self._ctx, C.c_void_p(x.data_ptr()), channels,
+                                         off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), int(off.size), up, down, hp, K,
+                                         C.c_void_p(out.data_ptr()), out_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         C.c_void_p(stream.cuda_stream)), self._ctx)
+        return out, out_off, out_cnt
+
     def digest(self, out, offsets, out_n, stream=None):
         """msg_digest of renders lying in a device output tensor ((frames, 2)
         float32, render i at frame offsets[i], out_n[i] frames): one record per

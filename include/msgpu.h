@@ -13,6 +13,7 @@
  *   msg_render_batch render(params) for N presets at once      (replaces MS:588)
  *   msg_plan_host    the render's scalar/RNG plan, host-side    (MS:589-646, 742-751)
  *   msg_digest       per-render checksums on the device         (MS:1585-1589)
+ *   msg_resample     sample-rate conversion of renders in HBM     (no counterpart: SURVEY §0)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
 #ifndef MSGPU_H
@@ -208,6 +209,25 @@ int msg_fft64(msg_ctx* ctx, int32_t n, int32_t inverse, const double* in, double
  * Enqueued on stream; one call in flight per context. */
 int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n_signals, const double* h,
             int64_t M, int32_t* fir_shape, void* stream);
+
+/* Rational sample-rate conversion by up / down of renders lying in HBM (DESIGN.md
+ * "Resampler"): a float32 polyphase FIR, zero-phase and zero-extended at both ends,
+ *   y[k] = up * sum_m h[k down + half - m up] x[m],  half = (K - 1) / 2,
+ *   0 <= m < n,  k < ceil(n up / down)
+ * (scipy.signal.resample_poly(x, up, down, window=h) with constant padding).
+ * x_dev: mono (channels = 1) or interleaved L/R (channels = 2) float32 signals in
+ * one device buffer, signal i at frame in_offsets[i] with in_n[i] frames (host
+ * arrays); y_dev receives signal i at frame out_offsets[i], ceil(in_n[i] up /
+ * down) frames; x_dev and y_dev must not alias.  h: K float64 taps in host
+ * memory, K odd (the prototype low-pass at the rate up x the input rate); they
+ * are uploaded as float32 with the gain up folded in.  up == down copies.
+ * MSG_E_UNSUPPORTED beyond the limits of csrc/resample.h: a phase-major tap table
+ * of up x ceil(K / up) floats over 2^20, or a tile's input span over 64 KiB.
+ * Enqueued on stream; one call in flight per context. */
+int msg_resample(msg_ctx* ctx, const float* x_dev, int32_t channels,
+                 const int64_t* in_offsets, const int64_t* in_n, int32_t n_signals,
+                 int32_t up, int32_t down, const double* h, int64_t K,
+                 float* y_dev, const int64_t* out_offsets, void* stream);
 
 /* The app's spectrogram stft_mag_db (MS:197-212) of a device buffer: x_dev is
  * n mono samples (channels = 1) or n interleaved L/R frames (channels = 2, the
