@@ -32,7 +32,8 @@
 #include "kernels_core.h"
 #include "launch.h"
 #include "host_pool.h"
-#include "tap_sort.h"
+#include "er_merge.h"
+#include "batch.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -634,6 +635,41 @@ static hipError_t wait_last(msg_ctx* ctx) {
     return ctx->done_armed ? hipEventSynchronize(ctx->done_ev) : hipSuccess;
 }
 
+#include "render_stages.h"
+
+// msg_fir: one PresetRt per signal (signal i at frame i * n of x and y) and its
+// jobs (i, j) for j = 0, step, 2 step, ... < nblk.
+static void sf_signals(int n_signals, int64_t n, int N, int P, int Q, int64_t B, int64_t nblk, int64_t step,
+                       std::vector<PresetRt>& prt, std::vector<int2>& jobs) {
+    prt.resize((size_t)n_signals);
+    jobs.reserve((size_t)(((nblk + step - 1) / step) * n_signals));
+    for (int i = 0; i < n_signals; ++i) {
+        PresetRt& r = prt[i];
+        memset(&r, 0, sizeof(r));
+        r.out_n = n;
+        r.y_off = (int64_t)i * n;
+        r.fir_on = 1; r.fir_N = N; r.fir_P = P; r.fir_Q = Q; r.fir_B = (int32_t)B;
+        for (int64_t j = 0; j < nblk; j += step) jobs.push_back(make_int2(i, (int)j));
+    }
+}
+
+// msg_fir's uploads: the records, the jobs, the spectrum jobs and the taps
+// (float for the k_fir8 engine, float64 for the IR-spectrum kernel).  Pageable
+// sources are staged before hipMemcpyAsync returns, so they may go afterwards.
+template <class T>
+static int sf_upload(msg_ctx* ctx, hipStream_t s, const std::vector<PresetRt>& prt, const std::vector<int2>& jobs,
+                     const int64_t* irjobs, size_t n_irjobs, DevBuf<T>& taps_dev, const T* taps, int64_t M) {
+    HIPCHK(ctx, ctx->sf_prt.ensure(prt.size()));
+    HIPCHK(ctx, ctx->sf_jobs.ensure(jobs.size()));
+    HIPCHK(ctx, taps_dev.ensure((size_t)M));
+    HIPCHK(ctx, ctx->sf_irjobs.ensure(n_irjobs));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->sf_prt.p, prt.data(), sizeof(PresetRt) * prt.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->sf_jobs.p, jobs.data(), sizeof(int2) * jobs.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(taps_dev.p, taps, sizeof(T) * (size_t)M, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->sf_irjobs.p, irjobs, sizeof(int64_t) * n_irjobs, hipMemcpyHostToDevice, s));
+    return MSG_OK;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -990,32 +1026,17 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
         // runs of consecutive blocks: about four per CU over the call, whole signals when they suffice
         const int64_t want = 4 * (int64_t)ctx->n_cu;
         const int run_len = (int)std::max<int64_t>(1, std::min<int64_t>(nb, (nb * n_signals + want - 1) / want));
-        std::vector<PresetRt> prt((size_t)n_signals);
+        std::vector<PresetRt> prt;
         std::vector<int2> runs;
-        for (int i = 0; i < n_signals; ++i) {
-            PresetRt& r = prt[i];
-            memset(&r, 0, sizeof(r));
-            r.out_n = n;
-            r.y_off = (int64_t)i * n;
-            r.fir_on = 1; r.fir_N = FIR8_N; r.fir_P = FIR8Q_P; r.fir_Q = (int32_t)nb; r.fir_B = FIR8Q_P;
-            for (int64_t j = 0; j < nb; j += run_len) runs.push_back(make_int2(i, (int)j));
-        }
-        std::vector<float> hf((size_t)M);
-        for (int64_t i = 0; i < M; ++i) hf[i] = (float)h[i];
+        sf_signals(n_signals, n, FIR8_N, FIR8Q_P, (int32_t)nb, FIR8Q_P, nb, run_len, prt, runs);
+        const std::vector<float> hf(h, h + M);
         const int64_t K8 = FIR8_HSTRIDE;          // float2 per spectrum (fir8_fft.h layout)
         const int64_t job[8] = {0, FIR8Q_P, 0, 0, FIR8Q_P, M - FIR8Q_P, K8, 0};   // H_0, H_1 from the float taps
         const unsigned grid = (unsigned)std::min<int64_t>((int64_t)runs.size(), ctx->n_cu);
-        HIPCHK(ctx, ctx->sf_prt.ensure(prt.size()));
-        HIPCHK(ctx, ctx->sf_jobs.ensure(runs.size()));
-        HIPCHK(ctx, ctx->sf_hf.ensure((size_t)M));
-        HIPCHK(ctx, ctx->sf_irjobs.ensure(8));
+        if (const int rc = sf_upload(ctx, s, prt, runs, job, 8, ctx->sf_hf, hf.data(), M)) return rc;
         HIPCHK(ctx, ctx->sf_hspec.ensure((size_t)(2 * K8)));
         HIPCHK(ctx, ctx->sf_xspec.ensure((size_t)grid * (size_t)fir8q_scratch_per_wg()));
         HIPCHK(ctx, fir8_counters(ctx, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sf_prt.p, prt.data(), sizeof(PresetRt) * prt.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sf_jobs.p, runs.data(), sizeof(int2) * runs.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sf_hf.p, hf.data(), sizeof(float) * (size_t)M, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sf_irjobs.p, job, sizeof(job), hipMemcpyHostToDevice, s));
         HIPCHK(ctx, launch_fir8_spec32(2, s, ctx->sf_irjobs.p, ctx->d_fir4tab, ctx->sf_hf.p, ctx->sf_hspec.p));
         HIPCHK(ctx, launch_fir8q((unsigned)runs.size(), run_len, grid, s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab,
                                  ctx->sf_hspec.p, x_dev, y_dev, ctx->sf_xspec.p, ctx->fir8_ctr.p));
@@ -1033,30 +1054,14 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
     if (blocks * n_signals > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many output blocks");
     if (fir_shape) { fir_shape[0] = N; fir_shape[1] = Pp; fir_shape[2] = Q; }
     if (N == FIR8_N) {   // one partition on k_fir8: H from the float taps by k_fir8_hpart
-        std::vector<PresetRt> prt((size_t)n_signals);
+        std::vector<PresetRt> prt;
         std::vector<int2> fj;
-        fj.reserve((size_t)(blocks * n_signals));
-        for (int i = 0; i < n_signals; ++i) {
-            PresetRt& r = prt[i];
-            memset(&r, 0, sizeof(r));
-            r.out_n = n;
-            r.y_off = (int64_t)i * n;
-            r.fir_on = 1; r.fir_N = N; r.fir_P = Pp; r.fir_Q = 1; r.fir_B = (int32_t)B;
-            r.h_off = 0; r.hs_off = 0; r.h_len = (int32_t)M;
-            for (int64_t b = 0; b < blocks; ++b) fj.push_back(make_int2(i, (int)b));
-        }
-        std::vector<float> hf((size_t)M);
-        for (int64_t i = 0; i < M; ++i) hf[i] = (float)h[i];
+        sf_signals(n_signals, n, N, Pp, 1, B, blocks, 1, prt, fj);
+        for (PresetRt& r : prt) r.h_len = (int32_t)M;
+        const std::vector<float> hf(h, h + M);
         const int64_t job[4] = {0, M, 0, 0};      // k_fir8_spec: taps [0, M) -> spectrum at 0
-        HIPCHK(ctx, ctx->sf_prt.ensure(prt.size()));
-        HIPCHK(ctx, ctx->sf_jobs.ensure(fj.size()));
-        HIPCHK(ctx, ctx->sf_hf.ensure((size_t)M));
-        HIPCHK(ctx, ctx->sf_irjobs.ensure(4));
+        if (const int rc = sf_upload(ctx, s, prt, fj, job, 4, ctx->sf_hf, hf.data(), M)) return rc;
         HIPCHK(ctx, ctx->sf_hspec.ensure((size_t)FIR8_HSTRIDE));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sf_prt.p, prt.data(), sizeof(PresetRt) * prt.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sf_jobs.p, fj.data(), sizeof(int2) * fj.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sf_hf.p, hf.data(), sizeof(float) * (size_t)M, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sf_irjobs.p, job, sizeof(job), hipMemcpyHostToDevice, s));
         HIPCHK(ctx, launch_fir8_spec32(1, s, ctx->sf_irjobs.p, ctx->d_fir4tab, ctx->sf_hf.p, ctx->sf_hspec.p));
         if (ctx->fir8p > 0) {   // persistent, as in the render (one workgroup per CU, per-XCD block counters)
             const int nj = (int)fj.size();
@@ -1081,30 +1086,14 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
     for (int q = 0; q < Q; ++q)
         jobs.insert(jobs.end(), {(int64_t)q * Pp, std::min<int64_t>(Pp, M - (int64_t)q * Pp), (int64_t)fp,
                                  (int64_t)q * K});
-    std::vector<PresetRt> prt((size_t)n_signals);
+    std::vector<PresetRt> prt;
     std::vector<int2> fj;
-    fj.reserve((size_t)(blocks * n_signals));
-    for (int i = 0; i < n_signals; ++i) {
-        PresetRt& r = prt[i];
-        memset(&r, 0, sizeof(r));
-        r.out_n = n;
-        r.y_off = (int64_t)i * n;
-        r.fir_on = 1; r.fir_N = N; r.fir_P = Pp; r.fir_Q = Q; r.fir_B = (int32_t)B;
-        r.h_off = 0;
-        r.fir_block_begin = (int32_t)(i * blocks);     // FDL: first segment spectrum of this signal
-        for (int64_t b = 0; b < blocks; ++b) fj.push_back(make_int2(i, (int)b));
-    }
-    HIPCHK(ctx, ctx->sf_prt.ensure(prt.size()));
-    HIPCHK(ctx, ctx->sf_jobs.ensure(fj.size()));
-    HIPCHK(ctx, ctx->sf_irjobs.ensure(jobs.size()));
-    HIPCHK(ctx, ctx->sf_h.ensure((size_t)M));
+    sf_signals(n_signals, n, N, Pp, Q, B, blocks, 1, prt, fj);
+    for (int i = 0; i < n_signals; ++i)
+        prt[i].fir_block_begin = (int32_t)(i * blocks);     // FDL: first segment spectrum of this signal
+    if (const int rc = sf_upload(ctx, s, prt, fj, jobs.data(), jobs.size(), ctx->sf_h, h, M)) return rc;
     HIPCHK(ctx, ctx->sf_hspec.ensure((size_t)Q * K));
     if (fdl) HIPCHK(ctx, ctx->sf_xspec.ensure((size_t)fj.size() * K));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->sf_prt.p, prt.data(), sizeof(PresetRt) * prt.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->sf_jobs.p, fj.data(), sizeof(int2) * fj.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->sf_irjobs.p, jobs.data(), sizeof(int64_t) * jobs.size(), hipMemcpyHostToDevice,
-                               s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->sf_h.p, h, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, launch_ir_spec((unsigned)Q, ctx->fir_plans.host[fp].lds_bytes, s, ctx->sf_irjobs.p, Q,
                                ctx->fir_plans.dev.p, ctx->sf_h.p, ctx->sf_hspec.p));
     int ti = 0;
@@ -1296,6 +1285,7 @@ int msg_last_grain64(msg_ctx* ctx, int32_t preset, int32_t k, double* grain, int
     return MSG_OK;
 }
 
+// The stages are in render_stages.h, in this order.
 int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
                      const double* bp_bank, int64_t bp_pairs, const double* const* irs, const int64_t* ir_lens, int32_t n_irs,
                      const uint8_t* const* images, const int32_t* img_h, const int32_t* img_w,
@@ -1306,1067 +1296,53 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     HIPCHK(ctx, stream_handover(ctx, s));
     DoneGuard done(ctx, s);
     collect_stage_set(ctx, ctx->ev_cur);   // this batch's event set: from two batches back
-    for (int p = 0; p < P; ++p) {
-        for (int l = 0; l < 4; ++l) {   // lanes inside the breakpoint bank
-            const int32_t nb = presets[p].n_bp[l], ob = presets[p].bp_off[l];
-            if (nb < 0 || (nb > 0 && (!bp_bank || ob < 0 || (int64_t)ob + nb > bp_pairs)))
-                return fail(ctx, MSG_E_ARG, "preset " + std::to_string(p) + ": breakpoint lane outside the bank");
-        }
-        const int ic = presets[p].ir_conv;
-        if (ic >= n_irs || (ic >= 0 && !irs)) return fail(ctx, MSG_E_ARG, "bad IR index");
-    }
+    Batch b;
+    b.presets = presets; b.P = P; b.bp_bank = bp_bank; b.bp_pairs = bp_pairs;
+    b.irs = irs; b.ir_lens = ir_lens; b.n_irs = n_irs;
+    b.images = images; b.img_h = img_h; b.img_w = img_w; b.n_images = n_images;
+    b.out_dev = out_dev; b.out_offsets = out_offsets; b.s = s;
+#define STAGE(f) do { if (const int rc_ = f(ctx, b)) return rc_; } while (0)
+    STAGE(stage_check);
     ctx->prof_batch = ctx->profiling && (ctx->prof_n++ % ctx->prof_every) == 0;
     stage_mark(ctx, 0, s);
-    using hclock = std::chrono::steady_clock;
-    const auto h0 = hclock::now();
-    auto hA = h0;
-    std::vector<int64_t> flen(P, 0);
-    for (int p = 0; p < P; ++p) {
-        const int f = presets[p].ir_frag;
-        flen[p] = (f >= 0 && f < n_irs) ? ir_lens[f] : 0;
-    }
-    std::vector<msg_plan_info> info(P);
-    std::vector<int32_t> slot_base(P), tap_base(P);
-    int64_t nslots = 0, ntaps = 0;
-    auto bases = [&]() -> int {
-        nslots = ntaps = 0;
-        int64_t frames = 0;
-        for (int p = 0; p < P; ++p) {
-            slot_base[p] = (int32_t)nslots;
-            tap_base[p] = (int32_t)ntaps;
-            nslots += info[p].n_slots;
-            if (presets[p].flags & MSG_F_ER_CLOUD) ntaps += std::max(1, presets[p].er_taps);
-            // kernels index a preset's frames with 32-bit integers (byte offsets
-            // from a tile's or block's own base; the tile counters of a batch in 32 bits)
-            if (info[p].out_n > MSG_MAX_FRAMES) return fail(ctx, MSG_E_UNSUPPORTED, "output longer than 2^31 - 2^20 frames");
-            frames += info[p].out_n;
-        }
-        if (nslots > INT32_MAX / 2) return fail(ctx, MSG_E_UNSUPPORTED, "too many events in one batch");
-        if (frames > ((int64_t)1 << 40)) return fail(ctx, MSG_E_UNSUPPORTED, "more than 2^40 frames in one batch");
-        return MSG_OK;
-    };
-    if (!ctx->device_plan) {
-        // ---- host plan (plan.h, the device planner's code) on the host pool:
-        // no device round trip, so the call returns once the batch is enqueued
-        HostPool& pool = HostPool::get();
-        pool.run(P, [&](int p) { msgplan::plan_sizes(presets[p], bp_bank, kHostZig, flen[p], info[p]); });
-        hA = hclock::now();
-        if (int st = bases()) return st;
-        ctx->h_events.resize(nslots);
-        ctx->h_er_off.resize(ntaps);
-        if (ctx->er_dev) {
-            ctx->h_er_key.resize(ntaps);
-            ctx->h_er_first.resize(ntaps);
-            ctx->h_er_cnt.resize(ntaps);
-        } else {
-            ctx->h_er_gain.resize(ntaps);
-        }
-        // offsets only: the gains (two thirds of the host plan of a 320-tap preset,
-        // a float64 exp each) are drawn on the device by k_er_gains
-        pool.run(P, [&](int p) {
-            const bool er = (presets[p].flags & MSG_F_ER_CLOUD) != 0;
-            msgplan::plan_events(presets[p], bp_bank, kHostZig, flen[p], p, info[p], ctx->h_events.data() + slot_base[p],
-                                 er ? ctx->h_er_off.data() + tap_base[p] : nullptr,
-                                 (er && !ctx->er_dev) ? ctx->h_er_gain.data() + tap_base[p] : nullptr, true);
-        });
-
-    } else {
-        // ---- device plan, phase 1: sizes ----
-        HIPCHK(ctx, ctx->frag_len.ensure(P));
-        HIPCHK(ctx, ctx->info.ensure(P));
-        HIPCHK(ctx, ctx->dp_presets.ensure(P));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dp_presets.p, presets, sizeof(msg_preset) * P, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->frag_len.p, flen.data(), sizeof(int64_t) * P, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, ctx->dp_bp.ensure((size_t)std::max<int64_t>(1, 2 * bp_pairs)));
-        if (bp_pairs > 0)
-            HIPCHK(ctx, hipMemcpyAsync(ctx->dp_bp.p, bp_bank, sizeof(double) * 2 * bp_pairs, hipMemcpyHostToDevice, s));
-        const int pb = 64;
-        hipLaunchKernelGGL(k_plan_sizes, dim3((P + pb - 1) / pb), dim3(pb), 0, s,
-                           ctx->dp_presets.p, P, ctx->dp_bp.p, ctx->frag_len.p, ctx->dzig, ctx->info.p);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(info.data(), ctx->info.p, sizeof(msg_plan_info) * P, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        // ---- phase 2: events + ER taps ----
-        if (int st = bases()) return st;
-        HIPCHK(ctx, ctx->slot_base.ensure(P));
-        HIPCHK(ctx, ctx->tap_base.ensure(P));
-        HIPCHK(ctx, ctx->dp_events.ensure(nslots));
-        HIPCHK(ctx, ctx->dp_er_off.ensure(ntaps));
-        HIPCHK(ctx, ctx->dp_er_gain.ensure(ntaps));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->slot_base.p, slot_base.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->tap_base.p, tap_base.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_plan_events, dim3((P + pb - 1) / pb), dim3(pb), 0, s,
-                           ctx->dp_presets.p, P, ctx->dp_bp.p, ctx->frag_len.p, ctx->dzig, ctx->slot_base.p,
-                           ctx->tap_base.p,
-                           ctx->dp_events.p, ctx->dp_er_off.p, ctx->dp_er_gain.p, ctx->info.p);
-        HIPCHK(ctx, hipGetLastError());
-        ctx->h_events.resize(nslots);
-        HIPCHK(ctx, hipMemcpyAsync(info.data(), ctx->info.p, sizeof(msg_plan_info) * P, hipMemcpyDeviceToHost, s));
-        if (nslots)
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_events.data(), ctx->dp_events.p, sizeof(msg_event) * nslots,
-                                       hipMemcpyDeviceToHost, s));
-        ctx->h_er_off.resize(ntaps);
-        ctx->h_er_gain.resize(ntaps);
-        if (ntaps) {
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_er_off.data(), ctx->dp_er_off.p, sizeof(int32_t) * ntaps,
-                                       hipMemcpyDeviceToHost, s));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_er_gain.data(), ctx->dp_er_gain.p, sizeof(double) * ntaps,
-                                       hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    }
-    // Early-reflection taps whose rounded delays coincide are merged here, in tap
-    // order and in float64 (the order MS:416-420 adds them), and the taps that
-    // act on the output (0 < offset < out_n, MS:418-420) are compacted to the
-    // front of the preset's tap range sorted by offset: k_h_build walks only the
-    // taps whose shifted IR overlaps its tile.  n_taps_live[p]: their count,
-    // tap_max[p]: the largest offset (0 without taps).
-    std::vector<int32_t> n_taps_live(P, 0), tap_max(P, 0);
-    {
-        auto merge = [&](int p) {
-            if (!(presets[p].flags & MSG_F_ER_CLOUD)) return;
-            const int nt = std::max(1, presets[p].er_taps);
-            int32_t* off = ctx->h_er_off.data() + tap_base[p];
-            const bool dev_gain = !ctx->device_plan && ctx->er_dev;
-            double* g = dev_gain ? nullptr : ctx->h_er_gain.data() + tap_base[p];
-            // (offset, tap index) packed in one key, sorted stably by offset (tap_sort.h)
-            thread_local std::vector<uint64_t> keybuf, tmpbuf;
-            thread_local std::vector<double> g0;
-            keybuf.resize(nt);
-            tmpbuf.resize(nt);
-            if (!dev_gain) g0.assign(g, g + nt);
-            const int64_t n = info[p].out_n;
-            int m = 0;
-            uint32_t omax = 0;
-            for (int k = 0; k < nt; ++k)
-                if (off[k] > 0 && off[k] < n) {
-                    keybuf[m++] = ((uint64_t)(uint32_t)off[k] << 32) | (uint32_t)k;
-                    omax = std::max(omax, (uint32_t)off[k]);
-                }
-            const uint64_t* key = sort_taps_by_offset(keybuf.data(), tmpbuf.data(), m, omax);
-            int live = 0;
-            if (dev_gain) {                              // slots -> key ranges, summed by k_er_gains
-                int32_t* kx = ctx->h_er_key.data() + tap_base[p];
-                int32_t* first = ctx->h_er_first.data() + tap_base[p];
-                int32_t* cnt = ctx->h_er_cnt.data() + tap_base[p];
-                for (int i = 0; i < m; ++i) kx[i] = (int32_t)(uint32_t)key[i];
-                for (int i = 0; i < m;) {
-                    const uint32_t o = (uint32_t)(key[i] >> 32);
-                    int j = i + 1;
-                    while (j < m && (uint32_t)(key[j] >> 32) == o) ++j;
-                    off[live] = (int32_t)o;
-                    first[live] = i;
-                    cnt[live] = j - i;
-                    ++live;
-                    i = j;
-                }
-            } else {
-                for (int i = 0; i < m;) {
-                    const uint32_t o = (uint32_t)(key[i] >> 32);
-                    double acc = g0[(uint32_t)key[i]];
-                    int j = i + 1;
-                    for (; j < m && (uint32_t)(key[j] >> 32) == o; ++j) acc += g0[(uint32_t)key[j]];
-                    off[live] = (int32_t)o;
-                    g[live] = acc;
-                    ++live;
-                    i = j;
-                }
-            }
-            n_taps_live[p] = live;
-            tap_max[p] = live ? off[live - 1] : 0;
-        };
-        if (ctx->device_plan) for (int p = 0; p < P; ++p) merge(p);
-        else HostPool::get().run(P, merge);
-    }
+    // ---- host: plan, records, one upload
+    b.h0 = Batch::hclock::now();
+    STAGE(stage_plan);
+    STAGE(stage_tap_merge);
     stage_mark(ctx, 1, s);
-    const auto h1 = hclock::now();
-    ctx->staging.add(&ctx->presets.p, presets, sizeof(msg_preset) * P);
-    ctx->staging.add(&ctx->events.p, ctx->h_events.data(), sizeof(msg_event) * nslots);
-    ctx->staging.add(&ctx->er_off.p, ctx->h_er_off.data(), sizeof(int32_t) * ntaps);
-    const bool er_dev = !ctx->device_plan && ctx->er_dev;
-    if (!er_dev) {
-        ctx->staging.add(&ctx->er_gain.p, ctx->h_er_gain.data(), sizeof(double) * ntaps);
-    } else {
-        ctx->staging.add(&ctx->er_key.p, ctx->h_er_key.data(), sizeof(int32_t) * ntaps);
-        ctx->staging.add(&ctx->er_first.p, ctx->h_er_first.data(), sizeof(int32_t) * ntaps);
-        ctx->staging.add(&ctx->er_cnt.p, ctx->h_er_cnt.data(), sizeof(int32_t) * ntaps);
-    }
-
-    // ---- host: runtime records ----
-    std::vector<PresetRt> prt(P);
-    // host EventRt records: a grow-only buffer reused across batches (a C5 sub-batch
-    // holds 512 k events; a fresh zero-filled vector cost ~8 ms of page faults and
-    // memset per batch).  Every slot an event list references is written below.
-    if ((size_t)nslots > ctx->h_ert_cap) {
-        ctx->h_ert.reset(new EventRt[(size_t)nslots + nslots / 4]);
-        ctx->h_ert_cap = (size_t)nslots + nslots / 4;
-    }
-    EventRt* const ert = ctx->h_ert.get();
-    // slots a preset reserves beyond its events are never written below: zero them
-    // so the whole uploaded range is defined
-    for (int p = 0; p < P; ++p)
-        if (info[p].n_slots > info[p].n_events)
-            memset(ert + slot_base[p] + info[p].n_events, 0,
-                   sizeof(EventRt) * (size_t)(info[p].n_slots - info[p].n_events));
-    std::vector<Fir64Rt> f64rt(P);
-    std::vector<int32_t> st_count(P);
-    int f64_cand = 0, f64_qmax = 0, f64_bmax = 0, f64_stmax = 0;
-    int64_t f64_hmax = 0;
-    std::vector<int32_t> gen_list, spec_small, spec_big, tile_begin(P), fir_begin(P), h_begin(P), st_begin(P),
-        fir_plan_of(P, 0);
-    std::vector<double> irbank;
-    std::vector<int64_t> ir_off(std::max(n_irs, 1), 0);
-    for (int i = 0; i < n_irs; ++i) {
-        ir_off[i] = (int64_t)irbank.size();
-        irbank.insert(irbank.end(), irs[i], irs[i] + ir_lens[i]);
-    }
-    int64_t pool = 0, ysum = 0, hsum = 0;
-    int32_t tiles = 0, fblocks = 0, hblocks = 0, stiles = 0;
-    int n_ola_fir = 0;                               // presets with PresetRt::ola_fir
-    int64_t ola_fir_nmax = 0;                        // their longest output
-    std::vector<int2> hpart_jobs;                  // (preset, q) of the presets on the k_fir4 engine
-    std::vector<int32_t> h_tile_begin(P, 0);       // k_h_build tiles per preset (prefix)
-    int32_t htiles = 0;
-    int32_t hblocks_gen = 0;                       // k_fir_h blocks of presets not on the k_fir4 engine
-    int64_t hs_sum = 0;
-    int spec_small_lds = 0, spec_big_lds = 0, fir_lds = 0;
-    std::vector<int32_t> spec_ct[SPEC_CT_PLANS];           // events of the compile-time spectral plans
-    const char* ct_env = getenv("MSGPU_SPEC_CT");         // "0": runtime-plan kernels only (tests)
-    const bool use_ct = !(ct_env && ct_env[0] == '0');
-    const char* s3_env = getenv("MSGPU_SPEC3");          // "0": no band-pruned kernel (A/B, tests)
-    const bool use_s3 = use_ct && !(s3_env && s3_env[0] == '0');
-    // MSGPU_G64_STOP=cep (tests only): float64-chain grains stop before the cepstral
-    // warp (MS:696-697), so meta grain_last is that stage's input (stage-pin tests)
-    const char* stop_env = getenv("MSGPU_G64_STOP");
-    const bool stop_cep = stop_env && std::strcmp(stop_env, "cep") == 0;
-    std::vector<int32_t> spec3;                           // events of the band-pruned kernel
-    std::vector<int32_t> f32_presets;                     // presets on the float32 chain
-    std::vector<int2> fjobs_by[6];                        // FIR output blocks per transform size; [5]: k_fir8
-    std::vector<int32_t> fir8_list;                       // ER presets on k_fir8 (N = 65536): k_fir8_hconv
-    std::vector<int32_t> ir_only8;                        // IR-only presets on k_fir8: H = the IR's spectrum
-    std::map<int, int64_t> ir8_spec_of;                   // IR index -> spectrum offset (before relocation)
-    std::vector<int64_t> ir8_jobs;                        // k_fir8_spec jobs: [ir_off, len, spec_off, 0]
-    int64_t ir8_sum = 0;
-    // the same at N = 32768 on the k_fir4 engine (k_fir4_hconv / k_fir4_irspec, MSGPU_FIR4C)
-    std::vector<int32_t> fir4c_list, ir_only4;
-    std::map<int, int64_t> ir4_spec_of;
-    std::vector<int64_t> ir4_jobs;
-    int64_t ir4_sum = 0;
-    // float64 grain chain records
-    std::vector<Ev64> ev64;
-    std::vector<int32_t> gen64_list;                      // normal-driven float64 events (event slots)
-    std::vector<int64_t> gen64_off;                       // their raw-normal offsets in micro64
-    std::vector<Chain64> chains;
-    std::vector<int32_t> last64(P, -1);
-    std::vector<uint8_t> imgbank;
-    std::vector<int64_t> img_off(std::max(n_images, 1), 0);
-    for (int i = 0; i < n_images; ++i) {
-        img_off[i] = (int64_t)imgbank.size();
-        imgbank.insert(imgbank.end(), images[i], images[i] + (int64_t)img_h[i] * img_w[i]);
-    }
-    int64_t sum64 = 0, save_sum = 0, state_sum = 0;
-    int64_t r2_sum = 0, so_M = 0;
-    std::vector<int32_t> odd_presets;
-    int g64_cap = 0;                                      // LDS slots of the LDS-class float64 grains
-    int64_t g64_big_cap = 0;                              // slot size of the global-class grains
-    std::vector<int32_t> g64_lds, g64_glb;                // Ev64 indices by class
-    std::vector<Chain64> chains_glb;
-    // Taps of the space filter h = (delta + ER) * IR of preset p (MS:409-445), 0
-    // without a FIR: the largest ER offset (planned span or actual) plus the IR
-    // length, at most out_n (later taps never reach y[:out_n]).
-    // full8: instead the length of the filter k_fir8's spectrum holds (every
-    // in-range tap, offset < out_n, and the whole IR), not capped at out_n.
-    auto h_taps = [&](int p, bool full8 = false) -> int64_t {
-        const msg_preset& pr = presets[p];
-        const bool er = (pr.flags & MSG_F_ER_CLOUD) != 0;
-        const int ic = pr.ir_conv;
-        const bool ir = (pr.flags & MSG_F_SPACE_IR) && ic >= 0 && ir_lens[ic] > 0;
-        if (!er && !ir) return 0;
-        const int64_t irl = ir ? std::min<int64_t>(ir_lens[ic], 8192) : 1;
-        const int64_t span = er ? std::max<int64_t>((int64_t)std::nearbyint(pr.er_max_ms / 1000.0 * (double)pr.base_sr),
-                                                    tap_max[p]) : 0;
-        if (full8) return std::min<int64_t>(span, std::max<int64_t>(0, info[p].out_n - 1)) + irl;
-        return std::max<int64_t>(1, std::min<int64_t>(span + irl, info[p].out_n));
-    };
-    // the per-preset pure functions of the records (FIR partitioning, stereo
-    // Bessel taps) in parallel; the loop below does the prefix bookkeeping
-    struct FirPick { int64_t M; int N, P, Q; float bess[25]; };
-    std::vector<FirPick> pick(P);
-    HostPool::get().run(P, [&](int p) {
-        FirPick& f = pick[p];
-        f.M = h_taps(p);
-        f.N = f.P = f.Q = 0;
-        if (f.M > 0) choose_fir(f.M, info[p].out_n, f.N, f.P, f.Q, ctx->fir8, h_taps(p, true));
-        const double w = std::min(std::max(presets[p].stereo_width, 0.0), 1.0);
-        for (int m = 0; m <= 12; ++m) {                // J_{-m} = (-1)^m J_m: one series per |m|
-            const double j = bessel_j(m, w * 0.9);
-            f.bess[m + 12] = (float)j;
-            f.bess[12 - m] = (float)((m & 1) ? -j : j);
-        }
-    });
-    // The overlap-add inside k_fir8p, decided for the batch as a whole: all of its
-    // k_fir8p presets or none, by their grains against their outputs.  A batch
-    // with any ola_fir preset runs the fused instantiation for all of its blocks,
-    // and that kernel's extra live state costs the plain blocks ~10 % (C3: a few
-    // sparse seeds had put every C3 batch on it, isolated FIR 1.88 -> 2.13 ms).
-    bool batch_ola = false;
-    if (ctx->ola_fir && ctx->fir8p > 0) {
-        double grains = 0.0, frames = 0.0;
-        for (int p = 0; p < P; ++p)
-            if (pick[p].M > 0 && pick[p].N == FIR8_N) {
-                grains += (double)info[p].pool_len;
-                frames += (double)info[p].out_n;
-            }
-        batch_ola = frames > 0.0 && grains <= ctx->ola_fir_density * frames;
-    }
-    for (int p = 0; p < P; ++p) {
-        const msg_preset& pr = presets[p];
-        const msg_plan_info& inf = info[p];
-        PresetRt& r = prt[p];
-        memset(&r, 0, sizeof(r));
-        r.out_n = inf.out_n;
-        r.out_off = out_offsets[p];
-        r.pool_base = pool;
-        r.y_off = ysum;
-        r.ev_begin = slot_base[p];
-        r.n_events = inf.n_events;
-        r.er_base = tap_base[p];
-        r.n_taps = n_taps_live[p];          // merged, in-range, offset-sorted taps
-        r.tile_begin = tiles;
-        r.max_n = inf.max_n;
-        // generator sources (MS:333-362)
-        r.frag_len = flen[p];
-        r.frag_off = (pr.ir_frag >= 0 && pr.ir_frag < n_irs) ? ir_off[pr.ir_frag] : 0;
-        if (pr.gen_mode == MSG_GEN_IMAGE && pr.image >= 0) {
-            if (pr.image >= n_images || !images) return fail(ctx, MSG_E_ARG, "bad image index");
-            r.img_off = img_off[pr.image];
-            r.img_h = img_h[pr.image];
-            r.img_w = img_w[pr.image];
-            if (r.img_h <= 0 || r.img_w <= 0) return fail(ctx, MSG_E_ARG, "empty image");
-        }
-        // ADSR (MS:173-177); A > n raises ValueError in the reference (MS:182)
-        const double sr = (double)pr.base_sr;
-        const int64_t A = std::max<int64_t>(0, (int64_t)std::nearbyint(sr * pr.env_a / 1000.0));
-        const int64_t D = std::max<int64_t>(0, (int64_t)std::nearbyint(sr * pr.env_d / 1000.0));
-        const int64_t R = std::max<int64_t>(0, (int64_t)std::nearbyint(sr * pr.env_r / 1000.0));
-        if (A > inf.out_n)
-            return fail(ctx, MSG_E_VALUE, "could not broadcast input array from shape (" + std::to_string(A) +
-                                              ",) into shape (" + std::to_string(inf.out_n) + ",)");
-        r.envA = (int32_t)A; r.envD = (int32_t)std::min<int64_t>(D, INT32_MAX);
-        r.envR = (int32_t)std::min<int64_t>(R, INT32_MAX);
-        r.envS = (float)std::min(std::max(pr.env_s, 0.0), 1.0);
-        r.envC = (float)std::max(1e-6, pr.env_curve);
-        {
-            const int64_t n = inf.out_n;
-            const int64_t j = std::min<int64_t>(n, A + D);
-            const int64_t s1 = std::max<int64_t>(j, n - R);
-            r.envJ = (int32_t)j;
-            r.envS1 = (int32_t)s1;
-            r.envInvA = A > 0 ? (float)(1.0 / (double)A) : 0.f;
-            r.envInvD = j > A ? (float)(1.0 / (double)(j - A)) : 0.f;
-            r.envInvR = n - s1 > 1 ? (float)(1.0 / (double)(n - s1 - 1)) : 0.f;
-        }
-        // space FIR
-        const bool er = (pr.flags & MSG_F_ER_CLOUD) != 0;
-        const int ic = pr.ir_conv;
-        const bool ir = (pr.flags & MSG_F_SPACE_IR) && ic >= 0 && ir_lens[ic] > 0;   // size<8 check: caller
-        r.ir_len = ir ? (int32_t)std::min<int64_t>(ir_lens[ic], 8192) : 0;
-        r.ir_off = ir ? ir_off[ic] : 0;
-        r.fir_on = (er || ir) ? 1 : 0;
-        r.fir_block_begin = fblocks;   // prefix arrays must stay monotone for find_preset
-        r.h_block_begin = hblocks;
-        r.h_fir4 = 0;
-        if (r.fir_on) {
-            const int64_t M = pick[p].M;
-            const int N = pick[p].N, Pp = pick[p].P, Q = pick[p].Q;
-            if (N != FIR8_N) {                     // runtime plan for k_fir_h (k_fir8 has its own engine)
-                std::string why;
-                const int fp = real_plan(ctx->fir_plans, N, why);
-                if (fp < 0) return fail(ctx, MSG_E_DEVICE, "FIR plan: " + why);
-                fir_plan_of[p] = fp;
-                fir_lds = std::max(fir_lds, ctx->fir_plans.host[fp].lds_bytes);
-            }
-            r.fir_N = N; r.fir_P = Pp; r.fir_Q = Q; r.fir_B = N - Pp + 1;
-            r.h_off = hsum;
-            r.h_len = (int32_t)M;
-            h_tile_begin[p] = htiles;
-            if (N == FIR8_N) {
-                // one partition: H = rfft(delta + ER taps) . S_IR straight into the spectrum
-                // (k_fir8_hconv), or the IR's spectrum itself for an IR-only preset
-                r.h_fir4 = 2;
-                const bool er = (pr.flags & MSG_F_ER_CLOUD) != 0;
-                int64_t irs = -1;
-                if (r.ir_len > 0) {
-                    auto it = ir8_spec_of.find(pr.ir_conv);
-                    if (it == ir8_spec_of.end()) {
-                        it = ir8_spec_of.emplace(pr.ir_conv, ir8_sum).first;
-                        ir8_jobs.insert(ir8_jobs.end(), {r.ir_off, (int64_t)r.ir_len, ir8_sum, 0});
-                        ir8_sum += (N / 2 + 1 + 15) & ~15;
-                    }
-                    irs = it->second;
-                }
-                if (er) {
-                    r.irs_off = irs;
-                    fir8_list.push_back(p);
-                } else {
-                    r.h_off = irs;                 // relocated past the per-preset spectra below
-                    ir_only8.push_back(p);
-                }
-            } else if (N == 2 * 16384 && ctx->fir4 && ctx->fir4c && Q == 1 && M <= N) {
-                // one partition on k_fir4: the k_fir8_hconv recipe at N = 32768 (fir4_fft.h),
-                // H = rfft(delta + ER taps) . S_IR, or S_IR itself for an IR-only preset
-                r.h_fir4 = 3;
-                const bool er = (pr.flags & MSG_F_ER_CLOUD) != 0;
-                int64_t irs = -1;
-                if (r.ir_len > 0) {
-                    auto it = ir4_spec_of.find(pr.ir_conv);
-                    if (it == ir4_spec_of.end()) {
-                        it = ir4_spec_of.emplace(pr.ir_conv, ir4_sum).first;
-                        ir4_jobs.insert(ir4_jobs.end(), {r.ir_off, (int64_t)r.ir_len, ir4_sum, 0});
-                        ir4_sum += (N / 2 + 1 + 15) & ~15;
-                    }
-                    irs = it->second;
-                }
-                if (er) {
-                    r.irs_off = irs;
-                    fir4c_list.push_back(p);
-                } else {
-                    r.h_off = irs;                 // relocated past the per-preset spectra below
-                    ir_only4.push_back(p);
-                }
-            } else {                               // h in the time domain (k_h_build), cut into partitions
-                r.hs_off = hs_sum;
-                hs_sum += (M + 3) & ~int64_t(3);    // 16-byte aligned h regions
-                htiles += (int32_t)((M + H_BUILD_TILE - 1) / H_BUILD_TILE);
-                if (N == 2 * 16384 && ctx->fir4) {   // k_fir4_hpart
-                    r.h_fir4 = 1;
-                    for (int q = 0; q < Q; ++q) hpart_jobs.push_back(make_int2(p, q));
-                }
-            }
-            const int32_t nblk = (int32_t)((inf.out_n + r.fir_B - 1) / r.fir_B);
-            // the overlap-add in k_fir8p's segment loads: each segment sums its grains
-            // again (N / B ~ 1.6 times per frame), worth it while the grains are sparse
-            if (N == FIR8_N && batch_ola) {
-                r.ola_fir = 1;
-                n_ola_fir++;
-                ola_fir_nmax = std::max<int64_t>(ola_fir_nmax, inf.out_n);
-            }
-            std::vector<int2>& fj = fjobs_by[N == FIR8_N ? 5 : __builtin_ctz(N) - 11];
-            for (int32_t b = 0; b < nblk; ++b) fj.push_back(make_int2(p, b));
-            fblocks += nblk;
-            hblocks += Q;
-            if (!r.h_fir4) hblocks_gen += Q;
-            // each preset's spectra start on a 128-byte boundary (N / 2 + 1 float2 per
-            // partition is odd: unpadded, every other preset's He straddled one more
-            // cache line per wave-wide load)
-            // (N = 65536: one spectrum of FIR8_HSTRIDE float2, Ho 128-byte aligned inside it)
-            static_assert(((FIR8_N / 2 + 1 + 15) & ~15) == FIR8_HSTRIDE, "fir8 spectrum stride");
-            if (!((N == FIR8_N || r.h_fir4 == 3) && r.ir_len > 0 && !(pr.flags & MSG_F_ER_CLOUD)))
-                hsum += ((int64_t)Q * (N / 2 + 1) + 15) & ~int64_t(15);
-        } else {
-            h_tile_begin[p] = htiles;
-        }
-        fir_begin[p] = r.fir_block_begin;
-        h_begin[p] = r.h_block_begin;
-        // stereo (MS:423-436)
-        const double w = std::min(std::max(pr.stereo_width, 0.0), 1.0);
-        const bool stereo = (pr.flags & MSG_F_STEREO) && inf.out_n >= 64;
-        r.stereo_fir = stereo ? 1 : 0;
-        if (stereo && (inf.out_n % 2)) {      // full-length rotation through Bluestein (kernels_stereo_odd.h)
-            const int64_t M = stereo_odd_len(inf.out_n, ctx->so_row, ctx->so_col);
-            if (M < 0)
-                return fail(ctx, MSG_E_UNSUPPORTED, "stereo diffusion of an odd output beyond the 2^34-point transform");
-            r.stereo_fir = 2;
-            r.r2_off = r2_sum;
-            r2_sum += (inf.out_n + 3) & ~int64_t(3);
-            so_M = std::max(so_M, M);
-            odd_presets.push_back(p);
-        }
-        r.dl = (int32_t)std::nearbyint((1 + 7 * w) * 0.0005 * sr);
-        r.dr = (int32_t)std::nearbyint((1 + 9 * w) * 0.0007 * sr);
-        std::memcpy(r.bess, pick[p].bess, sizeof(r.bess));
-        r.drive = (float)pr.sat_drive;
-        r.peak = (float)pr.peak;
-        st_begin[p] = stiles;
-        st_count[p] = (int32_t)((inf.out_n + ST_TILE - 1) / ST_TILE);
-        stiles += st_count[p];
-        {   // the float64 FIR's shape (kernels_fir64.h), for every FIR preset
-            Fir64Rt& f = f64rt[p];
-            f.h_len = r.fir_on ? (int32_t)pick[p].M : 0;
-            f.q = (f.h_len + FIR64_P - 1) / FIR64_P;
-            f.blocks = (int32_t)((inf.out_n + FIR64_B - 1) / FIR64_B);
-            f.st_tiles = st_count[p];
-            if (r.fir_on) {
-                f64_cand++;
-                f64_hmax = std::max<int64_t>(f64_hmax, f.h_len);
-                f64_qmax = std::max(f64_qmax, f.q);
-                f64_bmax = std::max(f64_bmax, f.blocks);
-                f64_stmax = std::max(f64_stmax, f.st_tiles);
-            }
-        }
-        if (!r.ola_fir) tiles += (int32_t)((inf.out_n + OLA_TILE - 1) / OLA_TILE);
-        pool += (inf.pool_len + 3) & ~int64_t(3);   // 16-byte aligned grain regions (float4 loads)
-        ysum += (inf.out_n + 3) & ~int64_t(3);   // keep every mono region 16-byte aligned
-        // events
-        bool precise = is_precise(pr);
-        if (!precise) {
-            // grains beyond the LDS-resident float32 spectral kernels run the float64
-            // chain in global memory (micro_ms up to 80 ms at 30 MHz: 2.4 M samples)
-            int last_n = -1;
-            for (int k = 0; k < inf.n_events && !precise; ++k) {
-                const msg_event& e = ctx->h_events[slot_base[p] + k];
-                if (!spec_ops(pr, e) || e.n == last_n) continue;   // each spectral grain length once
-                last_n = e.n;
-                if (use_ct && spectral_ct_plan(e.n) >= 0) continue;
-                std::string why;
-                const int pi = real_plan(ctx->grain_plans, e.n, why);
-                if (pi < 0) return fail(ctx, MSG_E_DEVICE, "grain plan: " + why);
-                const RealPlan& gp = ctx->grain_plans.host[pi];
-                if (gp.lds_bytes > LDS_MAX || gp.c.size > SPEC_M_BIG) precise = true;
-            }
-        }
-        if (precise && inf.n_events > 0) {
-            const bool chained = (pr.flags & (MSG_F_EVENT_FEEDBACK | MSG_F_IMPRINT)) != 0;
-            bool chain_global = false;
-            if (chained) {
-                Chain64 c;
-                memset(&c, 0, sizeof(c));
-                c.preset = p;
-                c.ev_begin = (int32_t)ev64.size();
-                c.n_events = inf.n_events;
-                c.prev_off = state_sum;
-                c.mem_off = state_sum + ((inf.max_n + 1) & ~1);
-                state_sum += ((inf.max_n + 1) & ~1) + ((inf.max_n / 2 + 2) & ~1);
-                chains.push_back(c);
-            }
-            const size_t ev_first = ev64.size();
-            for (int k = 0; k < inf.n_events; ++k) {
-                const int ei = slot_base[p] + k;
-                const msg_event& e = ctx->h_events[ei];
-                memset(&ert[ei], 0, sizeof(EventRt));
-                Ev64 v;
-                memset(&v, 0, sizeof(v));
-                std::string why;
-                v.plan = real64_plan(ctx->plans64, e.n, why);
-                if (v.plan < 0) return fail(ctx, MSG_E_DEVICE, "float64 grain plan: " + why);
-                const Real64Plan& gp = ctx->plans64.host[v.plan];
-                if (gp.cap > G64_SLOTS) {        // beyond the LDS engine: a global-memory slot
-                    g64_big_cap = std::max<int64_t>(g64_big_cap, gp.cap);
-                    g64_glb.push_back((int32_t)ev64.size());
-                    chain_global = true;
-                } else {
-                    g64_cap = std::max(g64_cap, gp.cap);
-                    g64_lds.push_back((int32_t)ev64.size());
-                }
-                v.ops = g64_ops(pr, e);
-                if (stop_cep && (v.ops & G64_CEP))   // debug: the grain as cepstral_warp receives it
-                    v.ops &= G64_LOWPASS | G64_WARP | G64_CHAIN;
-                v.n = e.n;
-                v.n0 = msgplan::grain_len(e.gen_sr, pr.micro_ms, 16);
-                v.gen_sr = e.gen_sr;
-                v.preset = p;
-                v.index = e.index;
-                v.ei = ei;
-                v.off64 = sum64;
-                v.grain_off = r.pool_base + e.pool_off;
-                v.cutoff_gen = e.cutoff_out * e.ufac;
-                v.stretch = e.stretch;
-                if (v.ops & G64_CEP) { v.save_off = save_sum; save_sum += e.n / 2 + 1; }
-                if (pr.gen_mode == MSG_GEN_WAVELET) {
-                    // morlet_atom is max(16, round(..)) long, the grain max(128, ..): shorter
-                    // atoms do not broadcast into the grain (MS:319, 166, 329)
-                    const int na = msgplan::grain_len(e.gen_sr, pr.micro_ms, 16);
-                    if (na < e.n)
-                        return fail(ctx, MSG_E_VALUE, "operands could not be broadcast together with shapes (" +
-                                                          std::to_string(e.n) + ",) (" + std::to_string(na) +
-                                                          ",) (" + std::to_string(e.n) + ",)");
-                }
-                if (normal_driven(pr.gen_mode)) {
-                    gen64_list.push_back(ei);
-                    gen64_off.push_back(sum64);
-                }
-                sum64 += (e.n + 1) & ~1;
-                last64[p] = (int32_t)ev64.size();
-                ev64.push_back(v);
-            }
-            (void)ev_first;
-            if (chained && chain_global) {                  // the chain walks big grains too
-                chains_glb.push_back(chains.back());
-                chains.pop_back();
-            }
-            continue;
-        }
-        f32_presets.push_back(p);
-    }
-    const auto hB = hclock::now();
-    // ---- float32-chain event records (EventRt), presets in parallel on the host
-    // pool; the per-kernel event lists are concatenated in preset order.  Events
-    // that need a runtime FFT plan (no compile-time plan for their length) are
-    // planned afterwards on this thread (the plan cache is not shared).
-    struct F32Lists { std::vector<int32_t> gen, s3, ct[SPEC_CT_PLANS], small, pending; };
-    std::vector<F32Lists> f32l(f32_presets.size());
-    HostPool::get().run((int)f32_presets.size(), [&](int i) {
-        const int p = f32_presets[i];
-        const msg_preset& pr = presets[p];
-        const PresetRt& r = prt[p];
-        F32Lists& L = f32l[i];
-        const double tilt = pr.gen_mode == MSG_GEN_FALLBACK ? -3.0 : pr.noise_tilt;
-        const double tilt_alpha = std::log(std::pow(10.0, tilt / 20.0)) / std::log(2.0);
-        const double env_tau = std::max(1e-6, (pr.micro_ms / 1000.0) * (pr.gen_mode == MSG_GEN_SKEWED ? 0.2 : 0.25));
-        const int ne = info[p].n_events;
-        L.gen.reserve(ne);
-        for (int k = 0; k < ne; ++k) {
-            const int ei = slot_base[p] + k;
-            const msg_event& e = ctx->h_events[ei];
-            EventRt& x = ert[ei];
-            memset(&x, 0, sizeof(x));
-            x.n = e.n;
-            x.gen_sr = e.gen_sr;
-            x.ops = spec_ops(pr, e);
-            x.cutoff_gen = e.cutoff_out * e.ufac;
-            x.roll = pr.bandlimit_roll_hz;
-            x.stretch = e.stretch;
-            x.tilt_alpha = tilt_alpha;
-            x.env_tau = env_tau;
-            x.warp_power = pr.nl_warp_power;
-            L.gen.push_back(ei);
-            const int ctp = (x.ops && use_ct) ? spectral_ct_plan(e.n) : -1;
-            if (use_s3 && x.ops &&
-                spec3_eligible(e.n, x.ops, x.gen_sr, x.cutoff_gen, x.roll, x.stretch, r.pool_base + e.pool_off,
-                               &x.s3_kb, &x.s3_kz, &x.s3_ky, &x.s3_inv_f, &x.s3_pad))
-                L.s3.push_back(ei);
-            else if (ctp >= 0)
-                L.ct[ctp].push_back(ei);
-            else if (x.ops)
-                L.pending.push_back(ei);
-            else
-                L.small.push_back(ei);
-        }
-    });
-    for (F32Lists& L : f32l) {
-        gen_list.insert(gen_list.end(), L.gen.begin(), L.gen.end());
-        spec3.insert(spec3.end(), L.s3.begin(), L.s3.end());
-        for (int c = 0; c < SPEC_CT_PLANS; ++c) spec_ct[c].insert(spec_ct[c].end(), L.ct[c].begin(), L.ct[c].end());
-        spec_small.insert(spec_small.end(), L.small.begin(), L.small.end());
-        for (int ei : L.pending) {
-            EventRt& x = ert[ei];
-            std::string why;
-            const int pi = real_plan(ctx->grain_plans, x.n, why);
-            if (pi < 0) return fail(ctx, MSG_E_DEVICE, "grain plan: " + why);
-            x.plan = pi;
-            const RealPlan& gp = ctx->grain_plans.host[pi];
-            if (gp.lds_bytes <= SPEC_SMALL_BYTES && gp.c.size <= SPEC_M_SMALL) {
-                spec_small.push_back(ei);
-                spec_small_lds = std::max(spec_small_lds, gp.lds_bytes);
-            } else if (gp.lds_bytes <= LDS_MAX && gp.c.size <= SPEC_M_BIG) {
-                spec_big.push_back(ei);
-                spec_big_lds = std::max(spec_big_lds, gp.lds_bytes);
-            } else {
-                return fail(ctx, MSG_E_UNSUPPORTED, "grain of " + std::to_string(x.n) +
-                            " samples exceeds the LDS-resident FFT (even n <= ~39900)");
-            }
-        }
-    }
-    const auto hC = hclock::now();
-    int f64_plan = -1;                                   // the float64 FIR's transform (kernels_fir64.h)
-    if (ctx->fir64 > 0 && f64_cand > 0) {
-        std::string why;
-        f64_plan = real64_plan(ctx->plans64, FIR64_N, why);
-        if (f64_plan < 0) return fail(ctx, MSG_E_DEVICE, "float64 FIR plan: " + why);
-    }
-    HIPCHK(ctx, sync_plans(ctx->grain_plans, s));
-    HIPCHK(ctx, sync_plans(ctx->fir_plans, s));
-    HIPCHK(ctx, sync_plans(ctx->plans64, s));
-    std::vector<int32_t> g64_list(g64_lds);
-    g64_list.insert(g64_list.end(), g64_glb.begin(), g64_glb.end());
-    const size_t n_lds_chains = chains.size();
-    chains.insert(chains.end(), chains_glb.begin(), chains_glb.end());
-    // global slots: persistent workgroups, at most ~8 GB of grain + scratch buffers
-    G64Global gg{};
-    unsigned g_grid = 0, c_grid = 0;
-    if (!g64_glb.empty() || !chains_glb.empty()) {
-        int64_t cap = g64_big_cap;
-        for (const Chain64& c : chains_glb)
-            for (int q = 0; q < c.n_events; ++q)
-                cap = std::max<int64_t>(cap, ctx->plans64.host[ev64[c.ev_begin + q].plan].cap);
-        gg.slot_cap = (cap + 1) & ~int64_t(1);
-        gg.mask_words = gg.slot_cap / 32 + 2;
-        const int64_t per_slot = 2 * gg.slot_cap * 16 + gg.mask_words * 4;
-        const int64_t lim = std::max<int64_t>(1, std::min<int64_t>(1024, (int64_t(8) << 30) / per_slot));
-        g_grid = (unsigned)std::min<int64_t>((int64_t)g64_glb.size(), lim);
-        c_grid = (unsigned)std::min<int64_t>((int64_t)chains_glb.size(), lim);
-        const int64_t slots = std::max<int64_t>(std::max(g_grid, c_grid), 1);
-        HIPCHK(ctx, ctx->g64A.ensure(slots * gg.slot_cap));
-        HIPCHK(ctx, ctx->g64B.ensure(slots * gg.slot_cap));
-        HIPCHK(ctx, ctx->g64mask.ensure(slots * gg.mask_words));
-        gg.A = ctx->g64A.p;
-        gg.B = ctx->g64B.p;
-        gg.mask = ctx->g64mask.p;
-    }
-    HIPCHK(ctx, ctx->micro64.ensure(sum64));
-    HIPCHK(ctx, ctx->grain64.ensure(sum64));
-    HIPCHK(ctx, ctx->save64.ensure(save_sum));
-    HIPCHK(ctx, ctx->state64.ensure(state_sum));
-    HIPCHK(ctx, ctx->so_r2.ensure(r2_sum));
-    HIPCHK(ctx, ctx->so_A.ensure(so_M));
-    std::vector<int2> fir_jobs;
-    int32_t fjob_off[7] = {0};
-    for (int i = 0; i < 6; ++i) {
-        fjob_off[i] = (int32_t)fir_jobs.size();
-        fir_jobs.insert(fir_jobs.end(), fjobs_by[i].begin(), fjobs_by[i].end());
-    }
-    fjob_off[6] = (int32_t)fir_jobs.size();
-    // the fused overlap-add's first event per k_fir8p block: the events of a
-    // preset are sorted by start, so one moving index per preset finds, block by
-    // block, the first event starting after the segment's start - max_n
-    std::vector<int32_t> fir_lo;
-    if (n_ola_fir > 0) {
-        const std::vector<int2>& fj = fjobs_by[5];
-        fir_lo.resize(fj.size());
-        int cur_p = -1, k = 0;
-        for (size_t j = 0; j < fj.size(); ++j) {
-            const int p = fj[j].x;
-            if (p != cur_p) { cur_p = p; k = 0; }
-            const PresetRt& r = prt[p];
-            const int64_t lim = (int64_t)fj[j].y * r.fir_B - (r.fir_P - 1) - (int64_t)r.max_n;
-            const msg_event* ev = ctx->h_events.data() + r.ev_begin;
-            if (fj[j].y == 0) k = 0;
-            while (k < r.n_events && (int64_t)ev[k].start <= lim) ++k;
-            fir_lo[j] = k;
-        }
-    }
-    HIPCHK(ctx, ctx->micro.ensure(pool));
-    HIPCHK(ctx, ctx->grain.ensure(pool));
-    HIPCHK(ctx, ctx->mono_a.ensure(ysum));
-    HIPCHK(ctx, ctx->mono_y.ensure(ysum));
-    // the IR spectra of the k_fir8 presets follow the per-preset spectra in hspec
-    for (int p : fir8_list)
-        if (prt[p].ir_len > 0) prt[p].irs_off += hsum;
-    for (int p : ir_only8) prt[p].h_off += hsum;
-    for (size_t j = 0; j < ir8_jobs.size(); j += 4) ir8_jobs[j + 2] += hsum;
-    // then the k_fir4_hconv presets' IR spectra
-    for (int p : fir4c_list)
-        if (prt[p].ir_len > 0) prt[p].irs_off += hsum + ir8_sum;
-    for (int p : ir_only4) prt[p].h_off += hsum + ir8_sum;
-    for (size_t j = 0; j < ir4_jobs.size(); j += 4) ir4_jobs[j + 2] += hsum + ir8_sum;
-    HIPCHK(ctx, ctx->hspec.ensure(hsum + ir8_sum + ir4_sum));
-    HIPCHK(ctx, ctx->hscratch.ensure(hs_sum));
-    auto h2d = [&](auto** dst, const auto* src, size_t bytes) -> hipError_t {
-        ctx->staging.add(dst, src, bytes);    // copied at the flush below, one copy for all
-        return hipSuccess;
-    };
-    for (int p = 0; p < P; ++p) tile_begin[p] = prt[p].tile_begin;
-    HIPCHK(ctx, h2d(&ctx->ert.p, ert, sizeof(EventRt) * nslots));
-    HIPCHK(ctx, h2d(&ctx->prt.p, prt.data(), sizeof(PresetRt) * P));
-    HIPCHK(ctx, h2d(&ctx->gen_list.p, gen_list.data(), sizeof(int32_t) * gen_list.size()));
-    HIPCHK(ctx, h2d(&ctx->spec_small.p, spec_small.data(), sizeof(int32_t) * spec_small.size()));
-    HIPCHK(ctx, h2d(&ctx->spec_big.p, spec_big.data(), sizeof(int32_t) * spec_big.size()));
-    std::vector<int32_t> ct_list;
-    int32_t ct_off[SPEC_CT_PLANS + 1] = {0};
-    for (int i = 0; i < SPEC_CT_PLANS; ++i) {
-        ct_off[i] = (int32_t)ct_list.size();
-        ct_list.insert(ct_list.end(), spec_ct[i].begin(), spec_ct[i].end());
-    }
-    ct_off[SPEC_CT_PLANS] = (int32_t)ct_list.size();
-    HIPCHK(ctx, h2d(&ctx->spec3_list.p, spec3.data(), sizeof(int32_t) * spec3.size()));
-    HIPCHK(ctx, h2d(&ctx->spec_ct_list.p, ct_list.data(), sizeof(int32_t) * ct_list.size()));
-    HIPCHK(ctx, h2d(&ctx->tile_begin.p, tile_begin.data(), sizeof(int32_t) * P));
-    HIPCHK(ctx, h2d(&ctx->fir_begin.p, fir_begin.data(), sizeof(int32_t) * P));
-    HIPCHK(ctx, h2d(&ctx->fir_jobs.p, fir_jobs.data(), sizeof(int2) * fir_jobs.size()));
-    HIPCHK(ctx, h2d(&ctx->fir_lo.p, fir_lo.data(), sizeof(int32_t) * fir_lo.size()));
-    HIPCHK(ctx, h2d(&ctx->h_begin.p, h_begin.data(), sizeof(int32_t) * P));
-    HIPCHK(ctx, h2d(&ctx->st_begin.p, st_begin.data(), sizeof(int32_t) * P));
-    HIPCHK(ctx, h2d(&ctx->fir_plan_of.p, fir_plan_of.data(), sizeof(int32_t) * P));
-    HIPCHK(ctx, h2d(&ctx->irbank.p, irbank.data(), sizeof(double) * irbank.size()));
-    HIPCHK(ctx, h2d(&ctx->h_tile_begin.p, h_tile_begin.data(), sizeof(int32_t) * P));
-    HIPCHK(ctx, h2d(&ctx->fir8_list.p, fir8_list.data(), sizeof(int32_t) * fir8_list.size()));
-    HIPCHK(ctx, h2d(&ctx->ir8_jobs.p, ir8_jobs.data(), sizeof(int64_t) * ir8_jobs.size()));
-    HIPCHK(ctx, h2d(&ctx->fir4c_list.p, fir4c_list.data(), sizeof(int32_t) * fir4c_list.size()));
-    HIPCHK(ctx, h2d(&ctx->ir4_jobs.p, ir4_jobs.data(), sizeof(int64_t) * ir4_jobs.size()));
-    HIPCHK(ctx, h2d(&ctx->hpart_jobs.p, hpart_jobs.data(), sizeof(int2) * hpart_jobs.size()));
-    if (ctx->maxbits_zero.size() < (size_t)P) ctx->maxbits_zero.assign((size_t)P, 0u);
-    HIPCHK(ctx, h2d(&ctx->maxbits.p, ctx->maxbits_zero.data(), sizeof(unsigned) * P));   // zeros in the one upload, no fill launch
-    // the float64 FIR chain: slots for up to FIR64_CAP flagged presets of the batch
-    const bool f64_on = ctx->fir64 > 0 && f64_cand > 0;
-    const int64_t f64_hstride = (f64_hmax + 3) & ~int64_t(3);
-    const int64_t f64_hsstride = (int64_t)f64_qmax * FIR64_K;
-    // slots per window: every flagged preset is served, FIR64_WINDOW_BYTES of h and H_q at a time
-    const int64_t f64_slot_bytes = f64_hstride * (int64_t)sizeof(float) + f64_hsstride * (int64_t)sizeof(double2);
-    const int f64_cap = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(f64_cand, ctx->fir64_cap),
-                                                                     FIR64_WINDOW_BYTES / std::max<int64_t>(1, f64_slot_bytes)));
-    if (f64_on) {
-        HIPCHK(ctx, ctx->f64_stats.ensure(2 * (size_t)P));
-        HIPCHK(ctx, ctx->f64_flag.ensure(P));
-        HIPCHK(ctx, ctx->st_part.ensure(2 * (size_t)stiles));
-        HIPCHK(ctx, ctx->f64_slot_preset.ensure(f64_cand));
-        HIPCHK(ctx, ctx->f64_nslots.ensure(1));
-        HIPCHK(ctx, ctx->f64_h.ensure((size_t)(f64_cap * f64_hstride)));
-        HIPCHK(ctx, ctx->f64_hs.ensure((size_t)(f64_cap * f64_hsstride)));
-        HIPCHK(ctx, h2d(&ctx->f64rt.p, f64rt.data(), sizeof(Fir64Rt) * P));
-    }
-    const int32_t n_odd = (int32_t)odd_presets.size();
-    HIPCHK(ctx, h2d(&ctx->st_count.p, st_count.data(), sizeof(int32_t) * P));
-    HIPCHK(ctx, h2d(&ctx->odd_list.p, odd_presets.data(), sizeof(int32_t) * odd_presets.size()));
-    HIPCHK(ctx, h2d(&ctx->odd_cnt.p, &n_odd, sizeof(int32_t)));
-    HIPCHK(ctx, h2d(&ctx->ev64.p, ev64.data(), sizeof(Ev64) * ev64.size()));
-    HIPCHK(ctx, h2d(&ctx->g64_list.p, g64_list.data(), sizeof(int32_t) * g64_list.size()));
-    HIPCHK(ctx, h2d(&ctx->gen64_list.p, gen64_list.data(), sizeof(int32_t) * gen64_list.size()));
-    HIPCHK(ctx, h2d(&ctx->gen64_off.p, gen64_off.data(), sizeof(int64_t) * gen64_off.size()));
-    HIPCHK(ctx, h2d(&ctx->chains.p, chains.data(), sizeof(Chain64) * chains.size()));
-    HIPCHK(ctx, h2d(&ctx->imgbank.p, imgbank.data(), imgbank.size()));
-    const auto h2 = hclock::now();
-    HIPCHK(ctx, ctx->staging.flush(s));
-    // the merged ER gains (host batch path): k_er_gains runs first in
-    // launch_h_spectra, before every filter kernel that reads them (the float64
-    // FIR's k_h64 comes later still), so it does not hold up the generator
-    const double* erg = ctx->er_gain.p;
-    if (er_dev) {
-        HIPCHK(ctx, ctx->er_gain_d.ensure((size_t)std::max<int64_t>(1, ntaps)));
-        HIPCHK(ctx, ctx->er_tap_d.ensure((size_t)std::max<int64_t>(1, ntaps)));
-        erg = ctx->er_gain_d.p;
-    }
-    if (ctx->prof_batch) {
-        const auto h3 = hclock::now();
-        ctx->host_sum[0] += std::chrono::duration<double, std::milli>(h1 - h0).count();
-        ctx->host_sum[1] += std::chrono::duration<double, std::milli>(h2 - h1).count();
-        ctx->host_sum[2] += std::chrono::duration<double, std::milli>(h3 - h2).count();
-        ctx->host_sum[3] += std::chrono::duration<double, std::milli>(hA - h0).count();
-        ctx->host_sum[4] += std::chrono::duration<double, std::milli>(h1 - hA).count();
-        ctx->host_sum[5] += std::chrono::duration<double, std::milli>(hB - h1).count();
-        ctx->host_sum[6] += std::chrono::duration<double, std::milli>(hC - hB).count();
-        ctx->host_sum[7] += std::chrono::duration<double, std::milli>(h2 - hC).count();
-        ctx->ola_fir_sum += n_ola_fir;
-        ++ctx->host_cnt;
-    }
-
-    // The filter spectra depend on the presets' taps and IRs only, not on the
-    // audio: launched before the generator (h_early), they run while
-    // the GPU holds the other streams' earlier stages, instead of queueing
-    // behind a persistent k_fir8p of another stream that holds every CU
-    // (C5's fir_h window had been ~100x its isolated time).
-    auto launch_h_spectra = [&]() -> int {
-        if (er_dev && ntaps > 0) {
-            hipLaunchKernelGGL(k_er_gains, dim3((unsigned)P), dim3(ER_T), 0, s, ctx->presets.p, ctx->prt.p, P,
-                               ctx->er_key.p, ctx->er_first.p, ctx->er_cnt.p, ctx->er_tap_d.p, ctx->er_gain_d.p);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        if (htiles > 0)
-            HIPCHK(ctx, launch_h_build((unsigned)htiles, s, ctx->prt.p, ctx->h_tile_begin.p, P, ctx->er_off.p,
-                                       erg, ctx->irbank.p, ctx->hscratch.p));
-        if (!ir8_jobs.empty())
-            HIPCHK(ctx, launch_fir8_spec64((unsigned)(ir8_jobs.size() / 4), s, ctx->ir8_jobs.p, ctx->d_fir4tab,
-                                           ctx->irbank.p, ctx->hspec.p));
-        if (!hpart_jobs.empty())
-            HIPCHK(ctx, launch_fir4_hpart(16384, (unsigned)hpart_jobs.size(), s, ctx->prt.p, ctx->hpart_jobs.p,
-                                          ctx->d_fir4tab, ctx->hscratch.p, ctx->hspec.p));
-        if (!fir8_list.empty())
-            HIPCHK(ctx, launch_fir8_hconv((unsigned)fir8_list.size(), s, ctx->prt.p, ctx->fir8_list.p, ctx->d_fir4tab,
-                                          ctx->er_off.p, erg, ctx->hspec.p));
-        if (!ir4_jobs.empty())
-            HIPCHK(ctx, launch_fir4_irspec((unsigned)(ir4_jobs.size() / 4), s, ctx->ir4_jobs.p, ctx->d_fir4tab,
-                                           ctx->irbank.p, ctx->hspec.p));
-        if (!fir4c_list.empty())
-            HIPCHK(ctx, launch_fir4_hconv((unsigned)fir4c_list.size(), s, ctx->prt.p, ctx->fir4c_list.p, ctx->d_fir4tab,
-                                          ctx->er_off.p, erg, ctx->hspec.p));
-        if (hblocks_gen > 0)   // blocks of k_fir4/k_fir8-engine presets return at once
-            HIPCHK(ctx, launch_fir_h((unsigned)hblocks, fir_lds, s, ctx->prt.p, ctx->h_begin.p, P,
-                                     ctx->fir_plans.dev.p, ctx->fir_plan_of.p, ctx->hscratch.p, ctx->hspec.p));
-        return MSG_OK;
-    };
-    int64_t fir_nmax = 0;
-    for (int p = 0; p < P; ++p)
-        if (prt[p].fir_on) fir_nmax = std::max<int64_t>(fir_nmax, prt[p].out_n);
-    const bool h_early = hblocks > 0 && (ctx->h_early == 1 || (ctx->h_early == 2 && fir_nmax >= ((int64_t)1 << 22)));
-    if (h_early) {
+    b.h1 = Batch::hclock::now();
+    STAGE(stage_preset_records);
+    b.hB = Batch::hclock::now();
+    STAGE(stage_event_records);
+    b.hC = Batch::hclock::now();
+    STAGE(stage_lists);
+    STAGE(stage_buffers);
+    STAGE(stage_upload);                   // takes h2 between its last add and the flush
+    host_clocks(ctx, b);
+    // ---- device: every launch of the batch
+    if (b.fir.h_early) {
         stage_mark(ctx, 10, s);
-        if (const int rc = launch_h_spectra()) return rc;
+        STAGE(enqueue_h_spectra);
         stage_mark(ctx, 11, s);
     }
-    // ---- generate ----
     stage_mark(ctx, 2, s);
-    if (!gen_list.empty())
-        hipLaunchKernelGGL(k_gen_normal<false>, dim3((unsigned)gen_list.size()), dim3(GEN_T), 0, s,
-                           ctx->presets.p, ctx->events.p, ctx->prt.p, ctx->gen_list.p, (int)gen_list.size(),
-                           ctx->dzig, ctx->d_jump, ctx->micro.p, (double*)nullptr, (const int64_t*)nullptr);
-    HIPCHK(ctx, hipGetLastError());
-    if (!gen64_list.empty())   // raw normals of the float64 chain's normal-driven generators
-        hipLaunchKernelGGL(k_gen_normal<true>, dim3((unsigned)gen64_list.size()), dim3(GEN_T), 0, s,
-                           ctx->presets.p, ctx->events.p, ctx->prt.p, ctx->gen64_list.p, (int)gen64_list.size(),
-                           ctx->dzig, ctx->d_jump, ctx->micro.p, ctx->micro64.p, (const int64_t*)ctx->gen64_off.p);
-    HIPCHK(ctx, hipGetLastError());
-    // ---- spectral chain ----
+    STAGE(enqueue_generate);
     stage_mark(ctx, 3, s);
-    if (!spec3.empty())
-        HIPCHK(ctx, launch_spec3((unsigned)spec3.size(), s, ctx->events.p, ctx->ert.p, ctx->prt.p, ctx->d_spec3_tab,
-                                 ctx->spec3_list.p, (int)spec3.size(), ctx->micro.p, ctx->grain.p));
-    for (int i = 0; i < SPEC_CT_PLANS; ++i)
-        if (ct_off[i + 1] > ct_off[i])
-            HIPCHK(ctx, launch_spectral_ct(i, (unsigned)(ct_off[i + 1] - ct_off[i]), s, ctx->events.p, ctx->ert.p,
-                                           ctx->prt.p, ctx->d_spec_ct_tab[i], ctx->spec_ct_list.p + ct_off[i],
-                                           ct_off[i + 1] - ct_off[i], ctx->micro.p, ctx->grain.p));
-    if (!spec_small.empty())
-        HIPCHK(ctx, launch_spectral(false, (unsigned)spec_small.size(), spec_small_lds, s, ctx->presets.p,
-                                    ctx->events.p, ctx->ert.p, ctx->prt.p, ctx->grain_plans.dev.p, ctx->spec_small.p,
-                                    (int)spec_small.size(), ctx->micro.p, ctx->grain.p));
-    if (!spec_big.empty())
-        HIPCHK(ctx, launch_spectral(true, (unsigned)spec_big.size(), spec_big_lds, s, ctx->presets.p,
-                                    ctx->events.p, ctx->ert.p, ctx->prt.p, ctx->grain_plans.dev.p, ctx->spec_big.p,
-                                    (int)spec_big.size(), ctx->micro.p, ctx->grain.p));
-    if (!g64_lds.empty())
-        HIPCHK(ctx, launch_grain64(nullptr, (unsigned)g64_lds.size(), g64_cap * 16, s, ctx->presets.p, ctx->ev64.p,
-                                   ctx->prt.p, ctx->plans64.dev.p, ctx->g64_list.p, (int)g64_lds.size(),
-                                   ctx->irbank.p, ctx->imgbank.p, ctx->dzig, ctx->micro64.p, ctx->grain64.p,
-                                   ctx->save64.p, ctx->grain.p));
-    if (!g64_glb.empty())
-        HIPCHK(ctx, launch_grain64(&gg, g_grid, 0, s, ctx->presets.p, ctx->ev64.p, ctx->prt.p, ctx->plans64.dev.p,
-                                   ctx->g64_list.p + g64_lds.size(), (int)g64_glb.size(), ctx->irbank.p,
-                                   ctx->imgbank.p, ctx->dzig, ctx->micro64.p, ctx->grain64.p, ctx->save64.p,
-                                   ctx->grain.p));
-    if (n_lds_chains > 0)
-        HIPCHK(ctx, launch_chain64(nullptr, (unsigned)n_lds_chains, g64_cap * 16, s, ctx->presets.p, ctx->ev64.p,
-                                   ctx->chains.p, (int)n_lds_chains, ctx->plans64.dev.p, ctx->grain64.p,
-                                   ctx->state64.p, ctx->grain.p));
-    if (!chains_glb.empty())
-        HIPCHK(ctx, launch_chain64(&gg, c_grid, 0, s, ctx->presets.p, ctx->ev64.p, ctx->chains.p + n_lds_chains,
-                                   (int)chains_glb.size(), ctx->plans64.dev.p, ctx->grain64.p, ctx->state64.p,
-                                   ctx->grain.p));
-    // ---- overlap-add x ADSR ----
+    STAGE(enqueue_spectral);
     stage_mark(ctx, 4, s);
-    if (tiles > 0) {
-        hipLaunchKernelGGL(k_ola_env, dim3((unsigned)tiles), dim3(OLA_T), 0, s, ctx->events.p, ctx->prt.p,
-                           ctx->tile_begin.p, P, ctx->grain.p, ctx->mono_a.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    // ---- FIR (presets without ER/IR pass a through) ----
+    STAGE(enqueue_ola);
     stage_mark(ctx, 5, s);
-    float* yb = ctx->mono_a.p;
-    if (hblocks > 0) {
-        if (!h_early)
-            if (const int rc = launch_h_spectra()) return rc;
-        stage_mark(ctx, 8, s);
-        for (int i = 0; i < 6; ++i) {
-            if (fjob_off[i + 1] <= fjob_off[i]) continue;
-            const unsigned nj = (unsigned)(fjob_off[i + 1] - fjob_off[i]);
-            if (i == 5 && ctx->fir8p > 0) {
-                // persistent: one workgroup per CU (at most one per block), a multiple of the XCD
-                // count.  Long outputs (h_early: milliseconds per launch) leave one CU in eight
-                // to the other streams' small kernels, which cannot start beside a k_fir8p
-                // workgroup (its VGPRs fill the CU): C5 118.4 - 119.4 ms with 224 of 256 CUs
-                // against 118.8 - 124.0 with all of them; C3 keeps every CU
-                const int cus = ctx->fir8p_cus > 0 ? std::min(ctx->fir8p_cus, ctx->n_cu)
-                                                   : (h_early ? ctx->n_cu - ctx->n_cu / 8 : ctx->n_cu);
-                const unsigned grid = (unsigned)std::max(MSG_XCDS, (std::min((int)nj, cus) / MSG_XCDS) * MSG_XCDS);
-                HIPCHK(ctx, fir8_counters(ctx, s));
-                HIPCHK(ctx, launch_fir8p(nj, grid, s, ctx->prt.p, ctx->fir_jobs.p + fjob_off[i],
-                                         ctx->d_fir4tab, ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p, ctx->fir8_ctr.p,
-                                         n_ola_fir > 0 ? ctx->events.p : nullptr, ctx->grain.p, ctx->fir_lo.p));
-            } else if (i == 5)
-                HIPCHK(ctx, launch_fir8(nj, s, ctx->prt.p, ctx->fir_jobs.p + fjob_off[i], ctx->d_fir4tab, ctx->hspec.p,
-                                        ctx->mono_a.p, ctx->mono_y.p));
-            else if (i == 4 && ctx->fir4)
-                HIPCHK(ctx, launch_fir4(16384, nj, s, ctx->prt.p, ctx->fir_jobs.p + fjob_off[i], ctx->d_fir4tab,
-                                        ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p));
-            else
-                HIPCHK(ctx, launch_fir2(1024 << i, nj, s, ctx->prt.p, ctx->fir_jobs.p + fjob_off[i],
-                                        ctx->d_fir2tab[i], ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p));
-        }
-        stage_mark(ctx, 9, s);
-        // presets with fir_on == 0 in a mixed batch: copy a -> y
-        for (int p = 0; p < P; ++p)
-            if (!prt[p].fir_on)
-                HIPCHK(ctx, hipMemcpyAsync(ctx->mono_y.p + prt[p].y_off, ctx->mono_a.p + prt[p].y_off,
-                                           sizeof(float) * prt[p].out_n, hipMemcpyDeviceToDevice, s));
-        yb = ctx->mono_y.p;
-    }
-    // ---- stereo, tanh, normalise ----
+    STAGE(enqueue_fir);                    // marks 8 and 9 around the FIR kernels
     stage_mark(ctx, 6, s);
-    // peak of L (and the float64 FIR's error predictor) over the float32 y
-    StereoSync sy{};
-    sy.flag64 = f64_on ? ctx->f64_flag.p : nullptr;
-    sy.part = f64_on ? ctx->st_part.p : nullptr;
-    sy.stats = f64_on ? ctx->f64_stats.p : nullptr;
-    sy.f64mode = f64_on ? ctx->fir64 : 0;
-    HIPCHK(ctx, launch_stereo_max((unsigned)stiles, s, ctx->prt.p, ctx->st_begin.p, P, yb, ctx->maxbits.p, sy));
-    if (f64_on)   // the float64 FIR's predictor per preset, from the tiles' partial sums
-        HIPCHK(ctx, launch_stereo_pred((unsigned)P, s, ctx->prt.p, ctx->st_begin.p, stiles, ctx->maxbits.p, sy));
-    if (f64_on) {   // flagged presets: the FIR again in float64, y overwritten (kernels_fir64.h)
-        Fir64Launch a;
-        a.rt = ctx->prt.p; a.n_presets = P; a.flag64 = ctx->f64_flag.p; a.maxbits = ctx->maxbits.p;
-        a.slot_preset = ctx->f64_slot_preset.p; a.n_slots = ctx->f64_nslots.p;
-        a.n_cand = f64_cand; a.cap = f64_cap;
-        a.fr = ctx->f64rt.p; a.tmax = (int)((f64_hmax + H_BUILD_TILE - 1) / H_BUILD_TILE); a.qmax = f64_qmax;
-        a.bmax = f64_bmax;
-        a.er_off = ctx->er_off.p; a.er_gain = erg; a.irbank = ctx->irbank.p;
-        a.h64 = ctx->f64_h.p; a.h_stride = f64_hstride; a.hs64 = ctx->f64_hs.p; a.hs_stride = f64_hsstride;
-        a.plans = ctx->plans64.dev.p; a.plan = f64_plan;
-        a.lds_bytes = FIR64_K * (int)sizeof(double2);   // the packed transform and its Nyquist slot
-        a.x = ctx->mono_a.p; a.y = yb;
-        HIPCHK(ctx, launch_fir64_flag(a, s));
-        if (n_ola_fir > 0) {   // the flagged ola_fir presets' mono a, which k_fir8p never wrote
-            const int tmax = (int)((ola_fir_nmax + OLA_TILE - 1) / OLA_TILE);
-            hipLaunchKernelGGL(k_ola_slots, dim3((unsigned)std::min<int64_t>((int64_t)f64_cand * tmax, 1024)),
-                               dim3(OLA_T), 0, s, ctx->events.p, ctx->prt.p, ctx->f64_slot_preset.p,
-                               ctx->f64_nslots.p, tmax, ctx->grain.p, ctx->mono_a.p);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        HIPCHK(ctx, launch_fir64(a, s));
-    }
-    ++ctx->batch_serial;
-    for (int p : odd_presets) {           // odd out_n: R = irfft(rfft(roll(y, -dr)) . rot) (MS:432-435)
-        const int64_t n = info[p].out_n;
-        auto it = ctx->so_bp.find(n);
-        if (it == ctx->so_bp.end()) {
-            // bound the cache (one entry per distinct odd length, for the
-            // life of the process): drop least-recently-used spectra of earlier
-            // batches while the cache holds more than 1 GiB (hipFree waits for them)
-            auto bytes = [&]() {
-                size_t b = 0;
-                for (auto& kv : ctx->so_bp) b += kv.second.cap * sizeof(double2);
-                return b;
-            };
-            while (bytes() > ((size_t)1 << 30)) {
-                int64_t victim = -1;
-                uint64_t oldest = ctx->batch_serial;
-                for (auto& kv : ctx->so_bp_use)
-                    if (kv.second < oldest) { oldest = kv.second; victim = kv.first; }
-                if (victim < 0) break;
-                ctx->so_bp[victim].release();
-                ctx->so_bp.erase(victim);
-                ctx->so_bp_use.erase(victim);
-            }
-            it = ctx->so_bp.emplace(n, DevBuf<double2>()).first;
-            HIPCHK(ctx, it->second.ensure(stereo_odd_len(n, ctx->so_row, ctx->so_col)));
-            HIPCHK(ctx, launch_stereo_odd_kernel(n, ctx->so_row, ctx->so_col, it->second.p, ctx->so_A.p, s));
-        }
-        ctx->so_bp_use[n] = ctx->batch_serial;
-        const double w = std::min(std::max(presets[p].stereo_width, 0.0), 1.0);
-        HIPCHK(ctx, launch_stereo_odd(n, ctx->so_row, ctx->so_col, prt[p].dr, w, yb + prt[p].y_off, it->second.p, ctx->so_A.p,
-                                      ctx->so_r2.p + prt[p].r2_off, s));
-    }
-    int odd_tmax = 0;
-    for (int p : odd_presets) odd_tmax = std::max(odd_tmax, st_count[p]);
-    if (f64_on)   // the float64 presets' peak from their new y (and R)
-        HIPCHK(ctx, launch_stereo_remax((unsigned)std::min<int64_t>((int64_t)f64_cand * f64_stmax, 256), s, ctx->prt.p, ctx->st_count.p,
-                                        ctx->f64_slot_preset.p, ctx->f64_nslots.p, f64_stmax, yb, ctx->so_r2.p,
-                                        ctx->maxbits.p));
-    if (n_odd > 0)   // odd lengths: the peak of the rotated R
-        HIPCHK(ctx, launch_stereo_remax((unsigned)std::min<int64_t>((int64_t)n_odd * odd_tmax, 4096), s, ctx->prt.p,
-                                        ctx->st_count.p, ctx->odd_list.p, ctx->odd_cnt.p, odd_tmax, yb, ctx->so_r2.p,
-                                        ctx->maxbits.p));
-    HIPCHK(ctx, launch_stereo_out((unsigned)stiles, s, ctx->prt.p, ctx->st_begin.p, P, yb, ctx->so_r2.p,
-                                  ctx->maxbits.p, out_dev));
+    STAGE(enqueue_stereo);
     stage_mark(ctx, 7, s);
+#undef STAGE
     HIPCHK(ctx, done.finish());
-    ctx->h_info = info;
-    ctx->h_prt = prt;
-    ctx->h_slot_base = slot_base;
-    ctx->h_ev64 = ev64;
-    ctx->h_last64 = last64;
-    ctx->last_n = P;
+    keep_mirrors(ctx, b);
     if (ctx->prof_batch) {
         ctx->pending[ctx->ev_cur] = true;
-        ctx->pending_fir[ctx->ev_cur] = hblocks > 0;
-        ctx->pending_h_early[ctx->ev_cur] = h_early;
+        ctx->pending_fir[ctx->ev_cur] = b.fir.hblocks > 0;
+        ctx->pending_h_early[ctx->ev_cur] = b.fir.h_early;
         ctx->ev_cur ^= 1;
     }
     return MSG_OK;

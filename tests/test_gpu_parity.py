@@ -144,6 +144,33 @@ def test_error_behaviour(msgpu):
         msgpu.render(msgpu.merged(out_dur_s=0.1, bp_density="1:2:3"))
 
 
+def test_batch_after_failed_batch(msgpu, irs):
+    """A batch that fails in the record stage leaves nothing queued for the
+    context's next upload: the next batch on the same engine (taps, events and
+    an image-free FIR staged) equals, bit for bit, its render on an engine that
+    never failed."""
+    import torch
+    from msgpu.engine import Engine
+    from msgpu.pack import PackedBatch
+    params = [msgpu.merged(out_dur_s=0.1, seed=31),
+              msgpu.config_params("C2", seed=1000, irs=irs, out_dur_s=0.25)]
+    outs = []
+    for fails_first in (True, False):
+        eng = Engine(0)
+        if fails_first:
+            bad = PackedBatch([msgpu.merged(out_dur_s=0.01, env_a=100.0)])   # attack longer than the buffer (MS:182)
+            with pytest.raises(ValueError):
+                eng.render_packed(bad)
+        packed = PackedBatch(params)
+        o = eng.render_packed(packed)
+        torch.cuda.synchronize(0)
+        outs.append(o.cpu().numpy())
+        eng.close()
+    assert outs[0].shape == outs[1].shape and outs[0].shape[0] == packed.total_frames
+    assert np.array_equal(outs[0], outs[1])
+    assert np.isfinite(outs[0]).all() and np.abs(outs[0]).max() > 0.0
+
+
 def test_fir_transform_sizes(msgpu, irs):
     """Every compile-time FIR transform size (N = 2048 .. 32768, one and two
     partitions), odd and even block alignments, ER-only / IR-only / both."""

@@ -80,3 +80,18 @@ def test_tap_sort_matches_std_sort(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     out = r.stdout + r.stderr
     assert r.returncode == 0 and "bad 0" in out, out[-4000:]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_er_merge_matches_brute_force(tmp_path):
+    """The per-preset early-reflection tap merge (csrc/er_merge.h) against a
+    std::map accumulated in tap order: the host-gain form's live count, sorted
+    offsets and gain bits, and the device-gain form's key ranges summed in
+    order, with offsets at and beyond both ends of the output -- under ASan + UBSan."""
+    exe = str(tmp_path / "er_merge_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-Wall", "-Werror", "-I", CSRC, "-o", exe, os.path.join(REPO, "tests", "er_merge_check.cpp")],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0 and "bad 0" in out, out[-4000:]
