@@ -35,293 +35,16 @@
 #include "er_merge.h"
 #include "batch.h"
 #include "../../include/msgpu.h"
+#include "ctx.h"
 
 namespace {
 
 const nprng::Zig kHostZig = {zig_ki_double, zig_wi_double, zig_fi_double,
                              zig_ke_double, zig_we_double, zig_fe_double};
 
-
 thread_local std::string g_err;   // errors before a context exists
-std::mutex g_gate_mu;              // msg_gate links between contexts
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;   // elements
-    hipError_t ensure(size_t n) {
-        if (n <= cap && p) return hipSuccess;
-        if (p) { hipFree(p); p = nullptr; cap = 0; }
-        size_t want = std::max<size_t>(n, 1);
-        want = want + want / 4;
-        hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-};
-
-// Pinned staging for a batch's host -> device uploads.  Every per-batch input
-// (presets, events, runtime records, job lists, IR bank ...) is packed into one
-// pinned slot and moved by ONE copy into a device arena; each input's device
-// pointer is then set to its place in the arena.  (One copy per input cost ~35
-// copy-engine blits per batch, ~2 ms of GPU time per C3 sub-batch.)  Two pinned
-// slots alternate between batches; a slot is refilled only after the copy that
-// read it (two batches back) has run, so msg_render_batch never waits on the
-// render stream.  The arena itself is reused in stream order.
-struct Staging {
-    struct Item { void** slot; const void* src; size_t bytes; };
-    struct Slot { char* host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool armed = false; };
-    Slot slot[2];
-    int cur = 0;
-    char* arena = nullptr;
-    size_t arena_cap = 0;
-    std::vector<Item> items;
-    template <class T> void add(T** dst, const T* src, size_t bytes) {
-        items.push_back(Item{reinterpret_cast<void**>(dst), src, bytes});
-    }
-    hipError_t flush(hipStream_t s) {
-        Slot& sl = slot[cur];
-        hipError_t e = hipSuccess;
-        if (!sl.done) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-        if (e == hipSuccess && sl.armed) e = hipEventSynchronize(sl.done);
-        std::vector<size_t> at(items.size());
-        size_t total = 0;
-        for (size_t i = 0; i < items.size(); ++i) {
-            at[i] = total;
-            total += (items[i].bytes + 255) & ~size_t(255);
-        }
-        total = std::max<size_t>(total, 256);
-        if (e == hipSuccess && total > sl.cap) {
-            if (sl.host) hipHostFree(sl.host);
-            sl.host = nullptr;
-            sl.cap = 0;
-            const size_t want = total + total / 4 + 4096;
-            e = hipHostMalloc((void**)&sl.host, want, hipHostMallocDefault);
-            if (e == hipSuccess) sl.cap = want;
-        }
-        if (e == hipSuccess && total > arena_cap) {     // growth frees the old arena (hipFree waits)
-            if (arena) hipFree(arena);
-            arena = nullptr;
-            arena_cap = 0;
-            const size_t want = total + total / 4 + 4096;
-            e = hipMalloc((void**)&arena, want);
-            if (e == hipSuccess) arena_cap = want;
-        }
-        if (e == hipSuccess) {   // pack in 1 MiB pieces on the host pool (C5: ~100 MB per sub-batch)
-            constexpr size_t PIECE = size_t(1) << 20;
-            std::vector<std::pair<size_t, size_t>> pieces;   // (item, byte offset in item)
-            for (size_t i = 0; i < items.size(); ++i)
-                for (size_t b = 0; b < items[i].bytes; b += PIECE) pieces.emplace_back(i, b);
-            HostPool::get().run((int)pieces.size(), [&](int k) {
-                const Item& it = items[pieces[k].first];
-                const size_t b = pieces[k].second;
-                std::memcpy(sl.host + at[pieces[k].first] + b, (const char*)it.src + b, std::min(PIECE, it.bytes - b));
-            });
-            size_t used = 0;
-            for (size_t i = 0; i < items.size(); ++i) used = at[i] + items[i].bytes;
-            if (used) e = hipMemcpyAsync(arena, sl.host, used, hipMemcpyHostToDevice, s);
-        }
-        for (size_t i = 0; i < items.size(); ++i) *items[i].slot = e == hipSuccess ? arena + at[i] : nullptr;
-        if (e == hipSuccess) e = hipEventRecord(sl.done, s);
-        sl.armed = e == hipSuccess;
-        items.clear();
-        cur ^= 1;
-        return e;
-    }
-    void release() {
-        for (Slot& sl : slot) {
-            if (sl.done) { hipEventSynchronize(sl.done); hipEventDestroy(sl.done); }
-            if (sl.host) hipHostFree(sl.host);
-            sl = Slot();
-        }
-        if (arena) hipFree(arena);
-        arena = nullptr;
-        arena_cap = 0;
-    }
-};
-
-// A per-batch input living in the Staging arena (set at each flush).
-template <class T> struct Slice { T* p = nullptr; };
-
-template <class P>
-struct PlanStoreT {
-    std::vector<P> host;                 // descriptors (device pointers inside)
-    std::vector<void*> allocs;
-    std::map<int, int> by_n;
-    bool dirty = false;
-    DevBuf<P> dev;
-};
-using PlanStore = PlanStoreT<RealPlan>;
-using Plan64Store = PlanStoreT<Real64Plan>;
 
 }  // namespace
-
-struct msg_ctx {
-    int device = 0;
-    std::string err;
-    bool profiling = false;
-    // msg_gate: this context's stream waits, before stage gate_wait, for the
-    // peer's gate event, and records its own after stage gate_rec begins
-    // (gate_peer / gated_by change under g_gate_mu: msg_gate, msg_destroy)
-    msg_ctx* gate_peer = nullptr;
-    std::vector<msg_ctx*> gated_by;   // contexts whose gate_peer is this one (cleared at msg_destroy)
-    int gate_wait = -1, gate_rec = -1;
-    hipEvent_t gate_ev = nullptr;
-    std::atomic<bool> gate_armed{false};   // gate_ev recorded at least once (read by the gated context)
-    // the stream of the last batch and an event at its end: a batch enqueued on
-    // another stream first waits for it (the staging arena and the per-batch
-    // buffers are reused in stream order only)
-    hipStream_t last_stream = nullptr;
-    hipEvent_t done_ev = nullptr;
-    bool done_armed = false;
-    // stage events: two sets alternate between batches; a set is read (folded
-    // into the sums) when it comes round again, two batches later, or at
-    // msg_stage_times -- profiling never makes the host wait for the last batch
-    bool pending[2] = {false, false};
-    bool pending_fir[2] = {false, false};
-    bool pending_h_early[2] = {false, false};
-    int ev_cur = 0;
-    // msg_set_profiling(ctx, k): batches 0, k, 2k, ... of the context record the
-    // stage events and host clocks (k = 1: every batch).  Each profiled batch
-    // adds 12 timed events to its stream and a host read of the set two batches
-    // back (bench.py samples every 4th batch)
-    int prof_every = 1;
-    int64_t prof_n = 0;
-    bool prof_batch = false;      // this batch records (profiling && its turn)
-    double stage_sum[10] = {0};   // accumulated stage times since msg_set_profiling(ctx, 1)
-    int64_t stage_cnt = 0;
-    // host wall clock per batch: plan, records, pinned upload, then the splits
-    // plan sizes, plan events + tap merge, preset records, event records, lists + buffers
-    double host_sum[8] = {0};
-    double ola_fir_sum = 0.0;    // presets whose overlap-add ran inside k_fir8p, summed over profiled batches
-    int64_t host_cnt = 0;
-    hipEvent_t ev[2][12] = {};
-    bool device_plan = false;     // MSGPU_DEVICE_PLAN=1: plan on the device (k_plan_*), read back
-    Staging staging;              // pinned uploads of a batch
-    // constant tables
-    uint64_t* d_ki = nullptr; double* d_wi = nullptr; double* d_fi = nullptr;
-    uint64_t* d_ke = nullptr; double* d_we = nullptr; double* d_fe = nullptr;
-    JumpTab* d_jump = nullptr;
-    float2* d_fir2tab[5] = {};   // k_fir2 twiddle tables, M = 1024 << i
-    float2* d_fir4tab = nullptr; // k_fir4 twiddle tables (M = 16384)
-    bool fir4 = true;            // M = 16384 blocks on k_fir4 (MSGPU_FIR4=0: k_fir2, A/B and tests)
-    // one-partition k_fir4 spectra from the taps (k_fir4_hconv; MSGPU_FIR4C=0: k_h_build + k_fir4_hpart)
-    bool fir4c = true;
-    bool fir8 = true;            // N = 65536 one-partition filters on k_fir8 (MSGPU_FIR8=0: off, A/B and tests)
-    int fir64 = 1;               // float64 FIR of saturated renders: 0 off, 1 predicted, 2 every FIR preset (MSGPU_FIR64)
-    int fir64_cap = FIR64_CAP;   // float64 FIR slots per window (MSGPU_FIR64_CAP: tests force several windows)
-    // k_fir8 blocks (MSGPU_FIR8P): 0 one workgroup per block, 1 persistent workgroups
-    // (one per CU, per-XCD block counters; C3 isolated FIR 2.03 -> 1.86 ms, C5 131.6
-    // -> 125.9 ms per step, profiles/r04r_ab.json)
-    int fir8p = 1;
-    bool fir8q = true;           // msg_fir: 32 k < M <= 64 k taps as two partitions on k_fir8q (MSGPU_FIR8Q=0: off)
-    int n_cu = 256;              // compute units (persistent grids)
-    int fir8p_cus = 0;           // persistent FIR workgroups (MSGPU_FIR8P_CUS, A/B; 0: one per CU)
-    // overlap-add inside k_fir8p's loads (PresetRt::ola_fir) for batches whose k_fir8p
-    // presets' grains total at most ola_fir_density x their frames (MSGPU_OLA_FIR=0: never)
-    bool ola_fir = true;
-    // filter spectra before the generator (MSGPU_H_EARLY): 0 at the FIR stage, 1 always,
-    // 2 (default) for batches with an output of at least 2^22 frames, whose FIR
-    // holds every CU for milliseconds (C5 -2.5 %); shorter ones lose by it (C3 +2 %)
-    int h_early = 2;
-    bool er_dev = true;          // ER gains drawn on the device (k_er_gains; MSGPU_ER_DEV=0: on the host plan)
-    double ola_fir_density = 1.25;
-    float2* d_spec_ct_tab[SPEC_CT_PLANS] = {};   // compile-time spectral plans (spec_ct.h)
-    float2* d_spec3_tab = nullptr;               // band-pruned spectral kernel (spec3.h)
-    Slice<int32_t> spec3_list;
-    nprng::Zig dzig{};
-    PlanStore grain_plans, fir_plans;
-    // per-batch buffers
-    // device planner (MSGPU_DEVICE_PLAN=1)
-    DevBuf<msg_preset> dp_presets;
-    DevBuf<double> dp_bp;                                 // breakpoint bank (device planner)
-    DevBuf<int64_t> frag_len;
-    DevBuf<msg_plan_info> info;
-    DevBuf<int32_t> slot_base, tap_base;
-    DevBuf<msg_event> dp_events;
-    DevBuf<int32_t> dp_er_off;
-    DevBuf<double> dp_er_gain;
-    // per-batch inputs, uploaded in one copy (Staging arena)
-    Slice<msg_preset> presets;
-    Slice<msg_event> events;
-    Slice<int32_t> er_off;
-    Slice<double> er_gain;
-    Slice<int32_t> er_key, er_first, er_cnt;
-    DevBuf<double> er_gain_d;           // k_er_gains' output (host batch path)
-    DevBuf<double> er_tap_d;            // k_er_gains' per-tap gains
-    Slice<EventRt> ert;
-    Slice<PresetRt> prt;
-    Slice<int32_t> gen_list, spec_small, spec_big, tile_begin, fir_begin, h_begin, st_begin, fir_plan_of;
-    DevBuf<float> micro, grain, mono_a, mono_y;
-    DevBuf<float2> hspec;
-    DevBuf<float> hscratch;                     // h of every FIR preset (k_h_build -> k_fir_h / k_fir4_hpart)
-    Slice<int32_t> h_tile_begin, fir8_list, fir_lo;
-    Slice<int64_t> ir8_jobs;
-    Slice<int32_t> fir4c_list;                  // k_fir4_hconv presets (one partition at N = 32768)
-    Slice<int64_t> ir4_jobs;                    // k_fir4_irspec jobs
-    Slice<int2> hpart_jobs;
-    Slice<int2> fir_jobs;
-    Slice<int32_t> spec_ct_list;
-    Slice<double> irbank;
-    Slice<unsigned> maxbits;            // per preset: k_stereo_max's peak bits, zeroed by the batch's upload
-    std::vector<unsigned> maxbits_zero;
-    // float64 space FIR of saturated renders (kernels_fir64.h)
-    Slice<Fir64Rt> f64rt;
-    Slice<int32_t> st_count, odd_list, odd_cnt;
-    DevBuf<double> f64_stats;                   // per preset: sum y^2, sum (1 + (d y)^2)^-2
-    DevBuf<int32_t> f64_flag, f64_slot_preset, f64_nslots;
-    DevBuf<double> st_part;             // stereo pass (kernels_stereo.h): per-tile partial sums
-    DevBuf<int32_t> fir8_ctr;           // k_fir8p's per-XCD block counters
-    DevBuf<float> f64_h;
-    DevBuf<double2> f64_hs;
-    // float64 grain chain (kernels_grain64.h)
-    Plan64Store plans64;
-    Slice<Ev64> ev64;
-    Slice<int32_t> g64_list, gen64_list;
-    Slice<int64_t> gen64_off;
-    DevBuf<double> micro64, grain64, state64;
-    DevBuf<double2> save64;
-    Slice<Chain64> chains;
-    Slice<uint8_t> imgbank;
-    DevBuf<double2> g64A, g64B;                 // global-class float64 grains (G64Global)
-    DevBuf<uint32_t> g64mask;
-    // standalone FIR (msg_fir): its own buffers, so it never touches a render batch's
-    DevBuf<PresetRt> sf_prt;
-    DevBuf<int2> sf_jobs;
-    DevBuf<int64_t> sf_irjobs;
-    DevBuf<double> sf_h;
-    DevBuf<float2> sf_hspec, sf_xspec;
-    DevBuf<float> sf_hf;                        // float taps of a k_fir8 filter
-    // msg_digest: render extents + tile bases, per-tile partials
-    DevBuf<int64_t> dg_meta;
-    DevBuf<char> dg_part;
-    // msg_resample: signal extents + tile bases, the tap table
-    DevBuf<int64_t> rs_meta;
-    DevBuf<float> rs_tab;
-    // odd-length stereo rotation (kernels_stereo_odd.h)
-    std::map<int64_t, DevBuf<double2>> so_bp;  // chirp kernel spectra by n (float64), LRU-bounded
-    std::map<int64_t, uint64_t> so_bp_use;     // batch serial of each entry's last use
-    uint64_t batch_serial = 0;
-    int so_row = 0, so_col = 0;                // transform-split limits (MSGPU_SO_ROW / _COL, tests; 0 = default)
-    DevBuf<double2> so_A;
-    DevBuf<float> so_r2;
-    // host mirrors of the last batch
-    std::vector<msg_plan_info> h_info;
-    std::vector<msg_event> h_events;
-    std::unique_ptr<EventRt[]> h_ert;   // host EventRt records (grow-only, msg_render_batch)
-    size_t h_ert_cap = 0;
-    std::vector<int32_t> h_er_off;
-    std::vector<double> h_er_gain;
-    // the host batch path's merged ER taps: per live slot its first key and
-    // key count, the keys' tap indices (k_er_gains draws the gains on the device)
-    std::vector<int32_t> h_er_key, h_er_first, h_er_cnt;
-    std::vector<PresetRt> h_prt;
-    std::vector<int32_t> h_slot_base;
-    std::vector<Ev64> h_ev64;
-    std::vector<int32_t> h_last64;      // per preset: Ev64 index of its last event, -1 = float32 chain
-    int32_t last_n = 0;
-};
 
 // the longest output a preset may have: every kernel indexes a preset's frames
 // with 32-bit integers (round 4 stopped at 2^29, where a 32-bit byte offset of
@@ -346,13 +69,13 @@ static int fail(msg_ctx* ctx, int code, const std::string& msg) {
 // ---------------------------------------------------------------------------
 // FFT plan creation
 // ---------------------------------------------------------------------------
-static hipError_t upload(PlanStore& ps, const std::vector<float>& v, const float2** out) {
-    void* d = nullptr;
-    hipError_t e = hipMalloc(&d, v.size() * sizeof(float));
-    if (e != hipSuccess) return e;
-    e = hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice);
-    ps.allocs.push_back(d);
-    *out = reinterpret_cast<const float2*>(d);
+// A plan's table (scalars S read as pairs V) on the device, owned by the store.
+template <class P, class S, class V>
+static hipError_t upload(PlanStoreT<P, S>& ps, const std::vector<S>& v, const V** out) {
+    DevBuf<S> d;
+    const hipError_t e = d.upload(v.data(), v.size());
+    *out = reinterpret_cast<const V*>(d.p);
+    ps.allocs.push_back(std::move(d));
     return e;
 }
 
@@ -413,16 +136,6 @@ static int real_plan(PlanStore& ps, int n, std::string& why) {
     return idx;
 }
 
-static hipError_t upload64(Plan64Store& ps, const std::vector<double>& v, const double2** out) {
-    void* d = nullptr;
-    hipError_t e = hipMalloc(&d, v.size() * sizeof(double));
-    if (e != hipSuccess) return e;
-    e = hipMemcpy(d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice);
-    ps.allocs.push_back(d);
-    *out = reinterpret_cast<const double2*>(d);
-    return e;
-}
-
 // float64 real-FFT plan for n samples (fft64.h); returns index or -1.
 static int real64_plan(Plan64Store& ps, int n, std::string& why) {
     auto it = ps.by_n.find(n);
@@ -446,7 +159,7 @@ static int real64_plan(Plan64Store& ps, int n, std::string& why) {
         std::vector<double> bs;
         fft64plan::chirp(m, tab);
         fft64plan::bluestein_spec(m, c.size, tab, bs);
-        if (upload64(ps, tab, &c.chirp) != hipSuccess || upload64(ps, bs, &c.bspec) != hipSuccess) {
+        if (upload(ps, tab, &c.chirp) != hipSuccess || upload(ps, bs, &c.bspec) != hipSuccess) {
             why = "hip upload failed";
             return -1;
         }
@@ -455,7 +168,7 @@ static int real64_plan(Plan64Store& ps, int n, std::string& why) {
     c.nrad = (int)rad.size();
     for (size_t i = 0; i < rad.size(); ++i) c.rad[i] = rad[i];
     fft64plan::twiddles(c.size, tab);
-    if (upload64(ps, tab, &c.tw) != hipSuccess) { why = "hip upload failed"; return -1; }
+    if (upload(ps, tab, &c.tw) != hipSuccess) { why = "hip upload failed"; return -1; }
     if (rp.even) {
         std::vector<double> rt(2 * (size_t)(m + 1));
         for (int k = 0; k <= m; ++k) {
@@ -463,7 +176,7 @@ static int real64_plan(Plan64Store& ps, int n, std::string& why) {
             rt[2 * k] = (double)cosl(a);
             rt[2 * k + 1] = (double)sinl(a);
         }
-        if (upload64(ps, rt, &rp.rt) != hipSuccess) { why = "hip upload failed"; return -1; }
+        if (upload(ps, rt, &rp.rt) != hipSuccess) { why = "hip upload failed"; return -1; }
     }
     rp.cap = std::max(std::max(c.size, rp.even ? m + 1 : n), n);
     const int idx = (int)ps.host.size();
@@ -473,14 +186,15 @@ static int real64_plan(Plan64Store& ps, int n, std::string& why) {
     return idx;
 }
 
-template <class P>
-static hipError_t sync_plans(PlanStoreT<P>& ps, hipStream_t s) {
+// The descriptors on the device; a store stays dirty until its copy has run.
+template <class P, class S>
+static hipError_t sync_plans(PlanStoreT<P, S>& ps, hipStream_t s) {
     if (!ps.dirty) return hipSuccess;
     hipError_t e = ps.dev.ensure(ps.host.size());
     if (e != hipSuccess) return e;
     e = hipMemcpyAsync(ps.dev.p, ps.host.data(), ps.host.size() * sizeof(P), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    ps.dirty = false;
+    if (e == hipSuccess) ps.dirty = false;
     return e;
 }
 
@@ -577,20 +291,21 @@ static int g64_ops(const msg_preset& p, const msg_event& e) {
 }
 
 static void stage_mark(msg_ctx* ctx, int i, hipStream_t s) {
-    if (ctx->gate_wait >= 0 || ctx->gate_rec >= 0) {
+    Gate& g = ctx->gate;
+    if (g.wait >= 0 || g.rec >= 0) {
         std::lock_guard<std::mutex> lk(g_gate_mu);   // the peer may be unlinked by msg_destroy
-        if (ctx->gate_peer) {
+        if (g.peer) {
             // the gate's wait comes before the stage's profiling event, so a stage's
             // time is its kernels' span on the stream, not the time it was held
-            if (i == ctx->gate_wait && ctx->gate_peer->gate_armed.load())
-                hipStreamWaitEvent(s, ctx->gate_peer->gate_ev, 0);
-            if (i == ctx->gate_rec) {
-                hipEventRecord(ctx->gate_ev, s);
-                ctx->gate_armed.store(true);
+            if (i == g.wait && g.peer->gate.armed.load())
+                hipStreamWaitEvent(s, g.peer->gate.ev, 0);
+            if (i == g.rec) {
+                hipEventRecord(g.ev, s);
+                g.armed.store(true);
             }
         }
     }
-    if (ctx->prof_batch) hipEventRecord(ctx->ev[ctx->ev_cur][i], s);
+    if (ctx->prof.batch) hipEventRecord(ctx->prof.ev[ctx->prof.cur][i], s);
 }
 
 // A batch on a different stream than the context's last one waits for that
@@ -601,7 +316,7 @@ static hipError_t stream_handover(msg_ctx* ctx, hipStream_t s) {
 }
 static hipError_t stream_done(msg_ctx* ctx, hipStream_t s) {
     if (!ctx->done_ev) {
-        const hipError_t e = hipEventCreateWithFlags(&ctx->done_ev, hipEventDisableTiming);
+        const hipError_t e = ctx->done_ev.create(hipEventDisableTiming);
         if (e != hipSuccess) return e;
     }
     ctx->last_stream = s;
@@ -697,12 +412,13 @@ msg_ctx* msg_create(int device_ordinal) {
     if (e != hipSuccess || ndev <= 0) { g_err = "no HIP device available"; return nullptr; }
     if (device_ordinal < 0 || device_ordinal >= ndev) { g_err = "bad device ordinal"; return nullptr; }
     if (hipSetDevice(device_ordinal) != hipSuccess) { g_err = "hipSetDevice failed"; return nullptr; }
+    // every early return frees what is already there through ~msg_ctx
     std::unique_ptr<msg_ctx> ctx(new msg_ctx());
     ctx->device = device_ordinal;
-    auto up = [&](auto*& dst, const auto* src, size_t n) {
-        using T = std::remove_pointer_t<std::remove_reference_t<decltype(dst)>>;
-        if (hipMalloc(&dst, n * sizeof(T)) != hipSuccess) return false;
-        return hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+    ctx->sw = Switches::from_env();
+    auto up = [](auto& dst, const auto* src, size_t n) { return dst.upload(src, n) == hipSuccess; };
+    auto up2 = [](DevBuf<float2>& dst, bool ok, const std::vector<float>& tab) {   // pairs of floats
+        return ok && dst.upload(reinterpret_cast<const float2*>(tab.data()), tab.size() / 2) == hipSuccess;
     };
     if (!up(ctx->d_ki, zig_ki_double, 256) || !up(ctx->d_wi, zig_wi_double, 256) ||
         !up(ctx->d_fi, zig_fi_double, 256) || !up(ctx->d_ke, zig_ke_double, 256) ||
@@ -710,7 +426,7 @@ msg_ctx* msg_create(int device_ordinal) {
         g_err = "uploading ziggurat tables failed";
         return nullptr;
     }
-    ctx->dzig = nprng::Zig{ctx->d_ki, ctx->d_wi, ctx->d_fi, ctx->d_ke, ctx->d_we, ctx->d_fe};
+    ctx->dzig = nprng::Zig{ctx->d_ki.p, ctx->d_wi.p, ctx->d_fi.p, ctx->d_ke.p, ctx->d_we.p, ctx->d_fe.p};
     JumpTab jt;
     for (int l = 0; l < GEN_T; ++l) {
         const nprng::Jump j = nprng::jump_of((uint64_t)l + 1);
@@ -728,58 +444,29 @@ msg_ctx* msg_create(int device_ordinal) {
         jt.fif[i] = (float)zig_fi_double[i];
     }
     if (!up(ctx->d_jump, &jt, 1)) { g_err = "uploading jump table failed"; return nullptr; }
-    for (int i = 0; i < 5; ++i) {
-        std::vector<float> tab;
-        if (!fir2_tables_host(1024 << i, tab) || !up(ctx->d_fir2tab[i], reinterpret_cast<float2*>(tab.data()),
-                                                     tab.size() / 2)) {
+    std::vector<float> tab;
+    for (int i = 0; i < 5; ++i)
+        if (!up2(ctx->d_fir2tab[i], fir2_tables_host(1024 << i, tab), tab)) {
             g_err = "uploading FIR twiddle tables failed";
             return nullptr;
         }
+    if (!up2(ctx->d_fir4tab, fir4_tables_host(16384, tab), tab)) {
+        g_err = "uploading FIR4 twiddle tables failed";
+        return nullptr;
     }
-    {
-        std::vector<float> tab;
-        if (!fir4_tables_host(16384, tab) || !up(ctx->d_fir4tab, reinterpret_cast<float2*>(tab.data()), tab.size() / 2)) {
-            g_err = "uploading FIR4 twiddle tables failed";
-            return nullptr;
-        }
-    }
-    if (const char* e = getenv("MSGPU_FIR4")) ctx->fir4 = e[0] != '0';
-    if (const char* e = getenv("MSGPU_FIR4C")) ctx->fir4c = e[0] != '0';
-    if (const char* e = getenv("MSGPU_FIR8")) ctx->fir8 = e[0] != '0';
-    if (const char* e = getenv("MSGPU_FIR64")) ctx->fir64 = atoi(e);
-    if (const char* e = getenv("MSGPU_FIR64_CAP")) ctx->fir64_cap = std::max(1, std::min(FIR64_CAP, atoi(e)));
-    if (const char* e = getenv("MSGPU_FIR8P")) ctx->fir8p = atoi(e);
-    if (const char* e = getenv("MSGPU_FIR8Q")) ctx->fir8q = e[0] != '0';
-    if (const char* e = getenv("MSGPU_FIR8P_CUS")) ctx->fir8p_cus = std::max(0, atoi(e));
-    if (const char* e = getenv("MSGPU_OLA_FIR")) ctx->ola_fir = e[0] != '0';
-    if (const char* e = getenv("MSGPU_H_EARLY")) ctx->h_early = atoi(e);
-    if (const char* e = getenv("MSGPU_ER_DEV")) ctx->er_dev = e[0] != '0';
-    if (const char* e = getenv("MSGPU_OLA_FIR_DENSITY")) ctx->ola_fir_density = atof(e);
-    {
-        int cu = 0;
-        if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cu >= MSG_XCDS)
-            ctx->n_cu = cu;
-    }
-    for (int i = 0; i < SPEC_CT_PLANS; ++i) {
-        std::vector<float> tab;
-        if (!spectral_ct_tables(i, tab) || !up(ctx->d_spec_ct_tab[i], reinterpret_cast<float2*>(tab.data()),
-                                               tab.size() / 2)) {
+    for (int i = 0; i < SPEC_CT_PLANS; ++i)
+        if (!up2(ctx->d_spec_ct_tab[i], spectral_ct_tables(i, tab), tab)) {
             g_err = "uploading spectral twiddle tables failed";
             return nullptr;
         }
+    if (!up2(ctx->d_spec3_tab, spec3_tables(tab), tab)) {
+        g_err = "uploading spectral twiddle tables failed";
+        return nullptr;
     }
-    {
-        std::vector<float> tab;
-        if (!spec3_tables(tab) || !up(ctx->d_spec3_tab, reinterpret_cast<float2*>(tab.data()), tab.size() / 2)) {
-            g_err = "uploading spectral twiddle tables failed";
-            return nullptr;
-        }
-    }
-    for (auto& set : ctx->ev)
-        for (auto& ev : set) hipEventCreate(&ev);
-    if (const char* e = getenv("MSGPU_DEVICE_PLAN")) ctx->device_plan = e[0] == '1';
-    if (const char* e = getenv("MSGPU_SO_ROW")) ctx->so_row = atoi(e);
-    if (const char* e = getenv("MSGPU_SO_COL")) ctx->so_col = atoi(e);
+    int cu = 0;
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cu >= MSG_XCDS)
+        ctx->n_cu = cu;
+    if (ctx->prof.create_events() != hipSuccess) { g_err = "creating the stage events failed"; return nullptr; }
     spectral_ct_init_attrs();
     spec3_init_attrs();
     spectral_init_attrs();
@@ -792,96 +479,28 @@ msg_ctx* msg_create(int device_ordinal) {
 }
 
 void msg_destroy(msg_ctx* ctx) {
-    if (!ctx) return;
-    hipSetDevice(ctx->device);
-    hipDeviceSynchronize();
-    for (PlanStore* ps : {&ctx->grain_plans, &ctx->fir_plans}) {
-        for (void* p : ps->allocs) hipFree(p);
-        ps->dev.release();
-    }
-    hipFree(ctx->d_ki); hipFree(ctx->d_wi); hipFree(ctx->d_fi);
-    hipFree(ctx->d_ke); hipFree(ctx->d_we); hipFree(ctx->d_fe); hipFree(ctx->d_jump);
-    for (float2* t : ctx->d_fir2tab) hipFree(t);
-    hipFree(ctx->d_fir4tab);
-    for (float2* t : ctx->d_spec_ct_tab) hipFree(t);
-    hipFree(ctx->d_spec3_tab);
-    ctx->sf_prt.release(); ctx->sf_jobs.release(); ctx->sf_irjobs.release(); ctx->sf_h.release();
-    ctx->sf_hspec.release(); ctx->sf_xspec.release(); ctx->sf_hf.release();
-    ctx->dg_meta.release(); ctx->dg_part.release();
-    ctx->rs_meta.release(); ctx->rs_tab.release();
-    for (auto& set : ctx->ev)
-        for (auto& ev : set) hipEventDestroy(ev);
-    {
-        std::lock_guard<std::mutex> lk(g_gate_mu);
-        for (msg_ctx* c : ctx->gated_by) { c->gate_peer = nullptr; c->gate_wait = c->gate_rec = -1; }
-        if (ctx->gate_peer) {
-            auto& v = ctx->gate_peer->gated_by;
-            v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
-        }
-    }
-    if (ctx->gate_ev) hipEventDestroy(ctx->gate_ev);
-    if (ctx->done_ev) hipEventDestroy(ctx->done_ev);
-    ctx->staging.release();
-    ctx->dp_presets.release(); ctx->dp_bp.release(); ctx->frag_len.release(); ctx->info.release(); ctx->slot_base.release();
-    ctx->tap_base.release(); ctx->dp_events.release(); ctx->dp_er_off.release(); ctx->dp_er_gain.release();
-    ctx->micro.release(); ctx->grain.release();
-    ctx->mono_a.release(); ctx->mono_y.release(); ctx->hspec.release();
-    ctx->hscratch.release();
-    ctx->f64_stats.release(); ctx->f64_flag.release();
-    ctx->fir8_ctr.release();
-    ctx->st_part.release(); ctx->f64_slot_preset.release(); ctx->f64_nslots.release();
-    ctx->f64_h.release(); ctx->f64_hs.release();
-    for (void* p : ctx->plans64.allocs) hipFree(p);
-    ctx->plans64.dev.release();
-    ctx->micro64.release(); ctx->grain64.release(); ctx->state64.release(); ctx->save64.release();
-    ctx->g64A.release(); ctx->g64B.release(); ctx->g64mask.release();
-    for (auto& kv : ctx->so_bp) kv.second.release();
-    ctx->so_A.release(); ctx->so_r2.release();
-    delete ctx;
+    if (ctx) delete ctx;
 }
 
-// Fold the event times of the last profiled batch into the running sums.
-// The events are read lazily (here, at the next batch of the same context or
-// at msg_stage_times) so profiling never blocks the host between batches.
-static void collect_stage_set(msg_ctx* ctx, int k) {
-    if (!ctx->pending[k]) return;
-    hipEvent_t* ev = ctx->ev[k];
-    hipEventSynchronize(ev[7]);
-    float ms[10] = {0};
-    for (int i = 0; i < 7; ++i) hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-    hipEventElapsedTime(&ms[7], ev[0], ev[7]);
-    if (ctx->pending_fir[k]) {   // the FIR kernel alone, and the filter spectra
-        hipEventElapsedTime(&ms[8], ev[8], ev[9]);
-        if (ctx->pending_h_early[k]) {   // launched before the generator: out of host_prep
-            hipEventElapsedTime(&ms[9], ev[10], ev[11]);
-            hipEventElapsedTime(&ms[1], ev[1], ev[10]);
-        } else {
-            hipEventElapsedTime(&ms[9], ev[5], ev[8]);
-        }
-    }
-    for (int i = 0; i < 10; ++i) ctx->stage_sum[i] += ms[i];
-    ++ctx->stage_cnt;
-    ctx->pending[k] = false;
-}
-// all sets (msg_stage_times / msg_set_profiling): waits for the profiled batches
-static void collect_stage_times(msg_ctx* ctx) {
-    collect_stage_set(ctx, ctx->ev_cur ^ 1);
-    collect_stage_set(ctx, ctx->ev_cur);
+// The owners' process-wide counts of what is live (dev_own.h): device
+// allocations, their bytes, pinned allocations, events.  Not part of the ABI.
+int msg_debug_live(int64_t out[4]) {
+    const devown::Live& l = devown::g_live;
+    out[0] = l.dev_n.load(devown::RLX);
+    out[1] = l.dev_bytes.load(devown::RLX);
+    out[2] = l.pinned_n.load(devown::RLX);
+    out[3] = l.events.load(devown::RLX);
+    return 0;
 }
 
 int msg_set_profiling(msg_ctx* ctx, int32_t on) {
     if (!ctx) return MSG_E_ARG;
-    collect_stage_times(ctx);
-    ctx->profiling = on != 0;
-    ctx->prof_every = on > 1 ? on : 1;
-    ctx->prof_n = 0;
-    if (ctx->profiling) {
-        for (double& v : ctx->stage_sum) v = 0.0;
-        for (double& v : ctx->host_sum) v = 0.0;
-        ctx->ola_fir_sum = 0.0;
-        ctx->stage_cnt = 0;
-        ctx->host_cnt = 0;
-    }
+    Prof& pr = ctx->prof;
+    pr.collect();
+    pr.on = on != 0;
+    pr.every = on > 1 ? on : 1;
+    pr.n = 0;
+    if (pr.on) pr.reset_sums();
     return MSG_OK;
 }
 
@@ -889,31 +508,32 @@ int msg_gate(msg_ctx* ctx, msg_ctx* peer, int32_t wait_stage, int32_t record_sta
     if (!ctx || peer == ctx || wait_stage < -1 || wait_stage > 9 || record_stage < -1 || record_stage > 9)
         return MSG_E_ARG;
     if (peer && peer->device != ctx->device) return MSG_E_ARG;
-    if (peer && !ctx->gate_ev && hipEventCreateWithFlags(&ctx->gate_ev, hipEventDisableTiming) != hipSuccess)
-        return fail(ctx, MSG_E_DEVICE, "hipEventCreate failed");
+    Gate& g = ctx->gate;
+    if (peer && !g.ev && g.ev.create(hipEventDisableTiming) != hipSuccess)
+        return fail(ctx, MSG_E_DEVICE, "creating the gate event failed");
     std::lock_guard<std::mutex> lk(g_gate_mu);
-    if (ctx->gate_peer) {
-        auto& v = ctx->gate_peer->gated_by;
+    if (g.peer) {
+        auto& v = g.peer->gate.gated_by;
         v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
     }
-    ctx->gate_peer = peer;
-    if (peer) peer->gated_by.push_back(ctx);
-    ctx->gate_wait = peer ? wait_stage : -1;
-    ctx->gate_rec = peer ? record_stage : -1;
-    ctx->gate_armed.store(false);
+    g.peer = peer;
+    if (peer) peer->gate.gated_by.push_back(ctx);
+    g.wait = peer ? wait_stage : -1;
+    g.rec = peer ? record_stage : -1;
+    g.armed.store(false);
     return MSG_OK;
 }
 
+// ms[0..9] stage times, [10..17] host clocks, [18] fused overlap-adds per batch
 int msg_stage_times(msg_ctx* ctx, float* ms, int32_t n) {
     if (!ctx || !ms) return MSG_E_ARG;
-    collect_stage_times(ctx);
+    Prof& pr = ctx->prof;
+    pr.collect();
     for (int i = 0; i < n && i < 10; ++i)
-        ms[i] = ctx->stage_cnt ? (float)(ctx->stage_sum[i] / (double)ctx->stage_cnt) : 0.f;
-    for (int i = 10; i < n && i < 13; ++i)
-        ms[i] = ctx->host_cnt ? (float)(ctx->host_sum[i - 10] / (double)ctx->host_cnt) : 0.f;
-    for (int i = 13; i < n && i < 18; ++i)
-        ms[i] = ctx->host_cnt ? (float)(ctx->host_sum[i - 10] / (double)ctx->host_cnt) : 0.f;
-    if (n > 18) ms[18] = ctx->host_cnt ? (float)(ctx->ola_fir_sum / (double)ctx->host_cnt) : 0.f;
+        ms[i] = pr.stage_cnt ? (float)(pr.stage_sum[i] / (double)pr.stage_cnt) : 0.f;
+    for (int i = 10; i < n && i < 18; ++i)
+        ms[i] = pr.host_cnt ? (float)(pr.host_sum[i - 10] / (double)pr.host_cnt) : 0.f;
+    if (n > 18) ms[18] = pr.host_cnt ? (float)(pr.ola_fir_sum / (double)pr.host_cnt) : 0.f;
     return MSG_OK;
 }
 
@@ -930,18 +550,17 @@ int msg_bench_fft(msg_ctx* ctx, int32_t n, int32_t reps, int32_t blocks, float* 
     HIPCHK(ctx, sync_plans(ps, nullptr));
     const RealPlan& rp = ps.host[pi];
     if (rp.lds_bytes > LDS_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too large for LDS");
-    float* sink = nullptr;
-    HIPCHK(ctx, hipMalloc(&sink, sizeof(float) * blocks));
-    hipEvent_t a, b;
-    hipEventCreate(&a); hipEventCreate(&b);
-    HIPCHK(ctx, launch_fft_bench(po2, blocks, rp.lds_bytes, nullptr, ps.dev.p, pi, 1, sink));   // warm-up
+    DevBuf<float> sink;
+    Event a, b;
+    HIPCHK(ctx, sink.alloc((size_t)blocks));
+    HIPCHK(ctx, a.create());
+    HIPCHK(ctx, b.create());
+    HIPCHK(ctx, launch_fft_bench(po2, blocks, rp.lds_bytes, nullptr, ps.dev.p, pi, 1, sink.p));   // warm-up
     hipEventRecord(a, nullptr);
-    HIPCHK(ctx, launch_fft_bench(po2, blocks, rp.lds_bytes, nullptr, ps.dev.p, pi, reps, sink));
+    HIPCHK(ctx, launch_fft_bench(po2, blocks, rp.lds_bytes, nullptr, ps.dev.p, pi, reps, sink.p));
     hipEventRecord(b, nullptr);
     HIPCHK(ctx, hipEventSynchronize(b));
     hipEventElapsedTime(ms_out, a, b);
-    hipEventDestroy(a); hipEventDestroy(b);
-    hipFree(sink);
     return MSG_OK;
 }
 
@@ -955,21 +574,16 @@ int msg_fft64(msg_ctx* ctx, int32_t n, int32_t inverse, const double* in, double
     HIPCHK(ctx, sync_plans(ctx->plans64, nullptr));
     const int K = n / 2 + 1;
     const size_t cnt = (size_t)std::max(n, 2 * K);
-    double* io = nullptr;
-    HIPCHK(ctx, hipMalloc(&io, cnt * sizeof(double)));
-    hipError_t e = hipMemcpy(io, in, (inverse ? 2 * K : n) * sizeof(double), hipMemcpyHostToDevice);
-    double2* gA = nullptr;
-    double2* gB = nullptr;
-    if (e == hipSuccess && rp.cap > G64_SLOTS) {     // beyond LDS: the engine's global ping-pong mode
-        e = hipMalloc(&gA, (size_t)rp.cap * sizeof(double2));
-        if (e == hipSuccess) e = hipMalloc(&gB, (size_t)rp.cap * sizeof(double2));
+    DevBuf<double> io;
+    DevBuf<double2> gA, gB;
+    HIPCHK(ctx, io.alloc(cnt));
+    HIPCHK(ctx, hipMemcpy(io.p, in, (inverse ? 2 * K : n) * sizeof(double), hipMemcpyHostToDevice));
+    if (rp.cap > G64_SLOTS) {     // beyond LDS: the engine's global ping-pong mode
+        HIPCHK(ctx, gA.alloc((size_t)rp.cap));
+        HIPCHK(ctx, gB.alloc((size_t)rp.cap));
     }
-    if (e == hipSuccess) e = launch_fft64_one(rp.cap * 16, nullptr, ctx->plans64.dev.p, pi, inverse ? 1 : 0, io, gA, gB);
-    if (e == hipSuccess) e = hipMemcpy(out, io, (inverse ? n : 2 * K) * sizeof(double), hipMemcpyDeviceToHost);
-    hipFree(io);
-    if (gA) hipFree(gA);
-    if (gB) hipFree(gB);
-    HIPCHK(ctx, e);
+    HIPCHK(ctx, launch_fft64_one(rp.cap * 16, nullptr, ctx->plans64.dev.p, pi, inverse ? 1 : 0, io.p, gA.p, gB.p));
+    HIPCHK(ctx, hipMemcpy(out, io.p, (inverse ? n : 2 * K) * sizeof(double), hipMemcpyDeviceToHost));
     return MSG_OK;
 }
 
@@ -1006,7 +620,7 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
     HIPCHK(ctx, stream_handover(ctx, s));
     DoneGuard done(ctx, s);
     int N = 0, Pp = 0, Q = 0;
-    choose_fir(M, n, N, Pp, Q, ctx->fir8);
+    choose_fir(M, n, N, Pp, Q, ctx->sw.fir8);
     // Many partitions: a frequency-domain delay line (fir_fft.h) computes each
     // input segment's spectrum once and reuses it for Q blocks -- two transforms
     // per block of N/2 outputs instead of Q + 1 per block of N - P + 1, for
@@ -1018,7 +632,7 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
     // per 32 768 outputs (MSGPU_FIR8Q=0: the choice above, k_fir4 at 64 k taps).
     // Above 35 748 taps the two partitions' 32 768-frame blocks beat one
     // partition's 65 537 - M (a k_fir8q block costs ~1.1 k_fir8p blocks).
-    if (ctx->fir8 && ctx->fir8q && ctx->fir8p > 0 && M <= 2 * (int64_t)FIR8Q_P &&
+    if (ctx->sw.fir8 && ctx->sw.fir8q && ctx->sw.fir8p > 0 && M <= 2 * (int64_t)FIR8Q_P &&
         (double)(FIR8_N + 1 - M) * 1.1 < (double)FIR8Q_P) {
         const int64_t nb = (n + FIR8Q_P - 1) / FIR8Q_P;
         if (nb * n_signals > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many output blocks");
@@ -1037,8 +651,8 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
         HIPCHK(ctx, ctx->sf_hspec.ensure((size_t)(2 * K8)));
         HIPCHK(ctx, ctx->sf_xspec.ensure((size_t)grid * (size_t)fir8q_scratch_per_wg()));
         HIPCHK(ctx, fir8_counters(ctx, s));
-        HIPCHK(ctx, launch_fir8_spec32(2, s, ctx->sf_irjobs.p, ctx->d_fir4tab, ctx->sf_hf.p, ctx->sf_hspec.p));
-        HIPCHK(ctx, launch_fir8q((unsigned)runs.size(), run_len, grid, s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab,
+        HIPCHK(ctx, launch_fir8_spec32(2, s, ctx->sf_irjobs.p, ctx->d_fir4tab.p, ctx->sf_hf.p, ctx->sf_hspec.p));
+        HIPCHK(ctx, launch_fir8q((unsigned)runs.size(), run_len, grid, s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab.p,
                                  ctx->sf_hspec.p, x_dev, y_dev, ctx->sf_xspec.p, ctx->fir8_ctr.p));
         HIPCHK(ctx, done.finish());
         return MSG_OK;
@@ -1062,15 +676,15 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
         const int64_t job[4] = {0, M, 0, 0};      // k_fir8_spec: taps [0, M) -> spectrum at 0
         if (const int rc = sf_upload(ctx, s, prt, fj, job, 4, ctx->sf_hf, hf.data(), M)) return rc;
         HIPCHK(ctx, ctx->sf_hspec.ensure((size_t)FIR8_HSTRIDE));
-        HIPCHK(ctx, launch_fir8_spec32(1, s, ctx->sf_irjobs.p, ctx->d_fir4tab, ctx->sf_hf.p, ctx->sf_hspec.p));
-        if (ctx->fir8p > 0) {   // persistent, as in the render (one workgroup per CU, per-XCD block counters)
+        HIPCHK(ctx, launch_fir8_spec32(1, s, ctx->sf_irjobs.p, ctx->d_fir4tab.p, ctx->sf_hf.p, ctx->sf_hspec.p));
+        if (ctx->sw.fir8p > 0) {   // persistent, as in the render (one workgroup per CU, per-XCD block counters)
             const int nj = (int)fj.size();
             const unsigned grid = (unsigned)std::max(MSG_XCDS, (std::min(nj, ctx->n_cu) / MSG_XCDS) * MSG_XCDS);
             HIPCHK(ctx, fir8_counters(ctx, s));
-            HIPCHK(ctx, launch_fir8p((unsigned)nj, grid, s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab,
+            HIPCHK(ctx, launch_fir8p((unsigned)nj, grid, s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab.p,
                                      ctx->sf_hspec.p, x_dev, y_dev, ctx->fir8_ctr.p, nullptr, nullptr, nullptr));
         } else {
-            HIPCHK(ctx, launch_fir8((unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab,
+            HIPCHK(ctx, launch_fir8((unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab.p,
                                     ctx->sf_hspec.p, x_dev, y_dev));
         }
         HIPCHK(ctx, done.finish());
@@ -1099,13 +713,13 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
     int ti = 0;
     while ((1024 << ti) != N / 2) ++ti;
     if (fdl)
-        HIPCHK(ctx, launch_fdl(N / 2, (unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir2tab[ti],
+        HIPCHK(ctx, launch_fdl(N / 2, (unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir2tab[ti].p,
                                ctx->sf_hspec.p, ctx->sf_xspec.p, x_dev, y_dev));
-    else if (N / 2 == 16384 && ctx->fir4)
-        HIPCHK(ctx, launch_fir4(N / 2, (unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab,
+    else if (N / 2 == 16384 && ctx->sw.fir4)
+        HIPCHK(ctx, launch_fir4(N / 2, (unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab.p,
                                 ctx->sf_hspec.p, x_dev, y_dev));
     else
-        HIPCHK(ctx, launch_fir2(N / 2, (unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir2tab[ti],
+        HIPCHK(ctx, launch_fir2(N / 2, (unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir2tab[ti].p,
                                 ctx->sf_hspec.p, x_dev, y_dev));
     // pageable-host H2D copies are staged before hipMemcpyAsync returns (as in
     // msg_render_batch), so the host vectors may go; the FIR runs asynchronously.
@@ -1295,7 +909,7 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, stream_handover(ctx, s));
     DoneGuard done(ctx, s);
-    collect_stage_set(ctx, ctx->ev_cur);   // this batch's event set: from two batches back
+    ctx->prof.collect_set(ctx->prof.cur);  // this batch's event set: from two batches back
     Batch b;
     b.presets = presets; b.P = P; b.bp_bank = bp_bank; b.bp_pairs = bp_pairs;
     b.irs = irs; b.ir_lens = ir_lens; b.n_irs = n_irs;
@@ -1303,7 +917,7 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
     b.out_dev = out_dev; b.out_offsets = out_offsets; b.s = s;
 #define STAGE(f) do { if (const int rc_ = f(ctx, b)) return rc_; } while (0)
     STAGE(stage_check);
-    ctx->prof_batch = ctx->profiling && (ctx->prof_n++ % ctx->prof_every) == 0;
+    ctx->prof.batch = ctx->prof.on && (ctx->prof.n++ % ctx->prof.every) == 0;
     stage_mark(ctx, 0, s);
     // ---- host: plan, records, one upload
     b.h0 = Batch::hclock::now();
@@ -1339,11 +953,11 @@ int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
 #undef STAGE
     HIPCHK(ctx, done.finish());
     keep_mirrors(ctx, b);
-    if (ctx->prof_batch) {
-        ctx->pending[ctx->ev_cur] = true;
-        ctx->pending_fir[ctx->ev_cur] = b.fir.hblocks > 0;
-        ctx->pending_h_early[ctx->ev_cur] = b.fir.h_early;
-        ctx->ev_cur ^= 1;
+    if (ctx->prof.batch) {
+        ctx->prof.pending[ctx->prof.cur] = true;
+        ctx->prof.pending_fir[ctx->prof.cur] = b.fir.hblocks > 0;
+        ctx->prof.pending_h_early[ctx->prof.cur] = b.fir.h_early;
+        ctx->prof.cur ^= 1;
     }
     return MSG_OK;
 }

@@ -1,6 +1,6 @@
 // render_stages.h — host: the stages of msg_render_batch, in the
-// order the call runs them.  Part of msgpu.hip, included once after msg_ctx,
-// HIPCHK, fail() and the plan caches; not a stand-alone header.  Each stage is
+// order the call runs them.  Part of msgpu.hip, included once after msg_ctx
+// (ctx.h), HIPCHK, fail() and the plan caches; not a stand-alone header.  Each stage is
 // a static int f(msg_ctx*, Batch&) that returns MSG_OK or the failure code
 // (with the context's error text set).
 #pragma once
@@ -52,7 +52,7 @@ static int plan_host(msg_ctx* ctx, Batch& b) {
     if (int st = plan_bases(ctx, b)) return st;
     ctx->h_events.resize(b.nslots);
     ctx->h_er_off.resize(b.ntaps);
-    if (ctx->er_dev) {
+    if (ctx->sw.er_dev) {
         ctx->h_er_key.resize(b.ntaps);
         ctx->h_er_first.resize(b.ntaps);
         ctx->h_er_cnt.resize(b.ntaps);
@@ -65,7 +65,7 @@ static int plan_host(msg_ctx* ctx, Batch& b) {
         const bool er = (b.presets[p].flags & MSG_F_ER_CLOUD) != 0;
         msgplan::plan_events(b.presets[p], b.bp_bank, kHostZig, b.flen[p], p, b.info[p],
                              ctx->h_events.data() + b.slot_base[p], er ? ctx->h_er_off.data() + b.tap_base[p] : nullptr,
-                             (er && !ctx->er_dev) ? ctx->h_er_gain.data() + b.tap_base[p] : nullptr, true);
+                             (er && !ctx->sw.er_dev) ? ctx->h_er_gain.data() + b.tap_base[p] : nullptr, true);
     });
     return MSG_OK;
 }
@@ -131,8 +131,8 @@ static int stage_plan(msg_ctx* ctx, Batch& b) {
     b.info.resize(b.P);
     b.slot_base.resize(b.P);
     b.tap_base.resize(b.P);
-    b.er_dev = !ctx->device_plan && ctx->er_dev;
-    return ctx->device_plan ? plan_device(ctx, b) : plan_host(ctx, b);
+    b.er_dev = !ctx->sw.device_plan && ctx->sw.er_dev;
+    return ctx->sw.device_plan ? plan_device(ctx, b) : plan_host(ctx, b);
 }
 
 // ---------------------------------------------------------------------------
@@ -151,7 +151,7 @@ static int stage_tap_merge(msg_ctx* ctx, Batch& b) {
                                          b.er_dev ? ctx->h_er_first.data() + tb : nullptr,
                                          b.er_dev ? ctx->h_er_cnt.data() + tb : nullptr, &b.tap_max[p]);
     };
-    if (ctx->device_plan) for (int p = 0; p < b.P; ++p) merge(p);
+    if (ctx->sw.device_plan) for (int p = 0; p < b.P; ++p) merge(p);
     else HostPool::get().run(b.P, merge);
     return MSG_OK;
 }
@@ -186,7 +186,7 @@ static void pick_fir(msg_ctx* ctx, Batch& b) {
         Batch::FirPick& f = pick[p];
         f.M = h_taps(b, p);
         f.N = f.P = f.Q = 0;
-        if (f.M > 0) choose_fir(f.M, b.info[p].out_n, f.N, f.P, f.Q, ctx->fir8, h_taps(b, p, true));
+        if (f.M > 0) choose_fir(f.M, b.info[p].out_n, f.N, f.P, f.Q, ctx->sw.fir8, h_taps(b, p, true));
         const double w = std::min(std::max(b.presets[p].stereo_width, 0.0), 1.0);
         for (int m = 0; m <= 12; ++m) {                // J_{-m} = (-1)^m J_m: one series per |m|
             const double j = bessel_j(m, w * 0.9);
@@ -200,14 +200,14 @@ static void pick_fir(msg_ctx* ctx, Batch& b) {
     // and that kernel's extra live state costs the plain blocks ~10 % (C3: a few
     // sparse seeds had put every C3 batch on it, isolated FIR 1.88 -> 2.13 ms).
     b.fir.batch_ola = false;
-    if (ctx->ola_fir && ctx->fir8p > 0) {
+    if (ctx->sw.ola_fir && ctx->sw.fir8p > 0) {
         double grains = 0.0, frames = 0.0;
         for (int p = 0; p < b.P; ++p)
             if (pick[p].M > 0 && pick[p].N == FIR8_N) {
                 grains += (double)b.info[p].pool_len;
                 frames += (double)b.info[p].out_n;
             }
-        b.fir.batch_ola = frames > 0.0 && grains <= ctx->ola_fir_density * frames;
+        b.fir.batch_ola = frames > 0.0 && grains <= ctx->sw.ola_fir_density * frames;
     }
 }
 
@@ -314,13 +314,13 @@ static int rec_space_fir(msg_ctx* ctx, Batch& b, int p) {
     r.h_len = (int32_t)M;
     if (N == FIR8_N) {
         place_one_partition(F.ir8, p, pr, r, 2);
-    } else if (N == 2 * 16384 && ctx->fir4 && ctx->fir4c && Q == 1 && M <= N) {
+    } else if (N == 2 * 16384 && ctx->sw.fir4 && ctx->sw.fir4c && Q == 1 && M <= N) {
         place_one_partition(F.ir4, p, pr, r, 3);
     } else {                               // h in the time domain (k_h_build), cut into partitions
         r.hs_off = F.hs_sum;
         F.hs_sum += (M + 3) & ~int64_t(3);    // 16-byte aligned h regions
         F.htiles += (int32_t)((M + H_BUILD_TILE - 1) / H_BUILD_TILE);
-        if (N == 2 * 16384 && ctx->fir4) {   // k_fir4_hpart
+        if (N == 2 * 16384 && ctx->sw.fir4) {   // k_fir4_hpart
             r.h_fir4 = 1;
             for (int q = 0; q < Q; ++q) F.hpart_jobs.push_back(make_int2(p, q));
         }
@@ -358,7 +358,7 @@ static int rec_stereo(msg_ctx* ctx, Batch& b, int p) {
     const bool stereo = (pr.flags & MSG_F_STEREO) && inf.out_n >= 64;
     r.stereo_fir = stereo ? 1 : 0;
     if (stereo && (inf.out_n % 2)) {      // full-length rotation through Bluestein (kernels_stereo_odd.h)
-        const int64_t M = stereo_odd_len(inf.out_n, ctx->so_row, ctx->so_col);
+        const int64_t M = stereo_odd_len(inf.out_n, ctx->sw.so_row, ctx->sw.so_col);
         if (M < 0)
             return fail(ctx, MSG_E_UNSUPPORTED, "stereo diffusion of an odd output beyond the 2^34-point transform");
         r.stereo_fir = 2;
@@ -658,7 +658,7 @@ static int stage_lists(msg_ctx* ctx, Batch& b) {
     Batch::Fir& F = b.fir;
     Batch::G64& G = b.g64;
     Batch::Fir64& S = b.f64;
-    if (ctx->fir64 > 0 && S.cand > 0) {                  // the float64 FIR's transform (kernels_fir64.h)
+    if (ctx->sw.fir64 > 0 && S.cand > 0) {                  // the float64 FIR's transform (kernels_fir64.h)
         std::string why;
         S.plan = real64_plan(ctx->plans64, FIR64_N, why);
         if (S.plan < 0) return fail(ctx, MSG_E_DEVICE, "float64 FIR plan: " + why);
@@ -701,18 +701,18 @@ static int stage_lists(msg_ctx* ctx, Batch& b) {
     b.f32.ct_off[SPEC_CT_PLANS] = (int32_t)b.f32.ct_list.size();
     b.n_odd = (int32_t)b.odd_presets.size();
     // the float64 FIR chain: slots for up to FIR64_CAP flagged presets of the batch
-    S.on = ctx->fir64 > 0 && S.cand > 0;
+    S.on = ctx->sw.fir64 > 0 && S.cand > 0;
     S.hstride = (S.hmax + 3) & ~int64_t(3);
     S.hsstride = (int64_t)S.qmax * FIR64_K;
     // slots per window: every flagged preset is served, FIR64_WINDOW_BYTES of h and H_q at a time
     const int64_t slot_bytes = S.hstride * (int64_t)sizeof(float) + S.hsstride * (int64_t)sizeof(double2);
-    S.cap = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(S.cand, ctx->fir64_cap),
+    S.cap = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(S.cand, ctx->sw.fir64_cap),
                                                         FIR64_WINDOW_BYTES / std::max<int64_t>(1, slot_bytes)));
     // filter spectra before the generator (MSGPU_H_EARLY)
     int64_t fir_nmax = 0;
     for (int p = 0; p < b.P; ++p)
         if (b.prt[p].fir_on) fir_nmax = std::max<int64_t>(fir_nmax, b.prt[p].out_n);
-    F.h_early = F.hblocks > 0 && (ctx->h_early == 1 || (ctx->h_early == 2 && fir_nmax >= ((int64_t)1 << 22)));
+    F.h_early = F.hblocks > 0 && (ctx->sw.h_early == 1 || (ctx->sw.h_early == 2 && fir_nmax >= ((int64_t)1 << 22)));
     return MSG_OK;
 }
 
@@ -845,19 +845,19 @@ static int enqueue_h_spectra(msg_ctx* ctx, Batch& b) {
         HIPCHK(ctx, launch_h_build((unsigned)F.htiles, s, ctx->prt.p, ctx->h_tile_begin.p, b.P, ctx->er_off.p,
                                    erg, ctx->irbank.p, ctx->hscratch.p));
     if (!F.ir8.jobs.empty())
-        HIPCHK(ctx, launch_fir8_spec64((unsigned)(F.ir8.jobs.size() / 4), s, ctx->ir8_jobs.p, ctx->d_fir4tab,
+        HIPCHK(ctx, launch_fir8_spec64((unsigned)(F.ir8.jobs.size() / 4), s, ctx->ir8_jobs.p, ctx->d_fir4tab.p,
                                        ctx->irbank.p, ctx->hspec.p));
     if (!F.hpart_jobs.empty())
         HIPCHK(ctx, launch_fir4_hpart(16384, (unsigned)F.hpart_jobs.size(), s, ctx->prt.p, ctx->hpart_jobs.p,
-                                      ctx->d_fir4tab, ctx->hscratch.p, ctx->hspec.p));
+                                      ctx->d_fir4tab.p, ctx->hscratch.p, ctx->hspec.p));
     if (!F.ir8.er_list.empty())
-        HIPCHK(ctx, launch_fir8_hconv((unsigned)F.ir8.er_list.size(), s, ctx->prt.p, ctx->fir8_list.p, ctx->d_fir4tab,
+        HIPCHK(ctx, launch_fir8_hconv((unsigned)F.ir8.er_list.size(), s, ctx->prt.p, ctx->fir8_list.p, ctx->d_fir4tab.p,
                                       ctx->er_off.p, erg, ctx->hspec.p));
     if (!F.ir4.jobs.empty())
-        HIPCHK(ctx, launch_fir4_irspec((unsigned)(F.ir4.jobs.size() / 4), s, ctx->ir4_jobs.p, ctx->d_fir4tab,
+        HIPCHK(ctx, launch_fir4_irspec((unsigned)(F.ir4.jobs.size() / 4), s, ctx->ir4_jobs.p, ctx->d_fir4tab.p,
                                        ctx->irbank.p, ctx->hspec.p));
     if (!F.ir4.er_list.empty())
-        HIPCHK(ctx, launch_fir4_hconv((unsigned)F.ir4.er_list.size(), s, ctx->prt.p, ctx->fir4c_list.p, ctx->d_fir4tab,
+        HIPCHK(ctx, launch_fir4_hconv((unsigned)F.ir4.er_list.size(), s, ctx->prt.p, ctx->fir4c_list.p, ctx->d_fir4tab.p,
                                       ctx->er_off.p, erg, ctx->hspec.p));
     if (F.hblocks_gen > 0)   // blocks of k_fir4/k_fir8-engine presets return at once
         HIPCHK(ctx, launch_fir_h((unsigned)F.hblocks, F.lds, s, ctx->prt.p, ctx->h_begin.p, b.P,
@@ -871,12 +871,12 @@ static int enqueue_generate(msg_ctx* ctx, Batch& b) {
     if (!gen.empty())
         hipLaunchKernelGGL(k_gen_normal<false>, dim3((unsigned)gen.size()), dim3(GEN_T), 0, b.s,
                            ctx->presets.p, ctx->events.p, ctx->prt.p, ctx->gen_list.p, (int)gen.size(),
-                           ctx->dzig, ctx->d_jump, ctx->micro.p, (double*)nullptr, (const int64_t*)nullptr);
+                           ctx->dzig, ctx->d_jump.p, ctx->micro.p, (double*)nullptr, (const int64_t*)nullptr);
     HIPCHK(ctx, hipGetLastError());
     if (!gen64.empty())   // raw normals of the float64 chain's normal-driven generators
         hipLaunchKernelGGL(k_gen_normal<true>, dim3((unsigned)gen64.size()), dim3(GEN_T), 0, b.s,
                            ctx->presets.p, ctx->events.p, ctx->prt.p, ctx->gen64_list.p, (int)gen64.size(),
-                           ctx->dzig, ctx->d_jump, ctx->micro.p, ctx->micro64.p, (const int64_t*)ctx->gen64_off.p);
+                           ctx->dzig, ctx->d_jump.p, ctx->micro.p, ctx->micro64.p, (const int64_t*)ctx->gen64_off.p);
     HIPCHK(ctx, hipGetLastError());
     return MSG_OK;
 }
@@ -887,12 +887,12 @@ static int enqueue_spectral(msg_ctx* ctx, Batch& b) {
     const Batch::G64& G = b.g64;
     hipStream_t s = b.s;
     if (!F.spec3.empty())
-        HIPCHK(ctx, launch_spec3((unsigned)F.spec3.size(), s, ctx->events.p, ctx->ert.p, ctx->prt.p, ctx->d_spec3_tab,
+        HIPCHK(ctx, launch_spec3((unsigned)F.spec3.size(), s, ctx->events.p, ctx->ert.p, ctx->prt.p, ctx->d_spec3_tab.p,
                                  ctx->spec3_list.p, (int)F.spec3.size(), ctx->micro.p, ctx->grain.p));
     for (int i = 0; i < SPEC_CT_PLANS; ++i)
         if (F.ct_off[i + 1] > F.ct_off[i])
             HIPCHK(ctx, launch_spectral_ct(i, (unsigned)(F.ct_off[i + 1] - F.ct_off[i]), s, ctx->events.p, ctx->ert.p,
-                                           ctx->prt.p, ctx->d_spec_ct_tab[i], ctx->spec_ct_list.p + F.ct_off[i],
+                                           ctx->prt.p, ctx->d_spec_ct_tab[i].p, ctx->spec_ct_list.p + F.ct_off[i],
                                            F.ct_off[i + 1] - F.ct_off[i], ctx->micro.p, ctx->grain.p));
     if (!F.spec_small.empty())
         HIPCHK(ctx, launch_spectral(false, (unsigned)F.spec_small.size(), F.small_lds, s, ctx->presets.p,
@@ -945,28 +945,28 @@ static int enqueue_fir(msg_ctx* ctx, Batch& b) {
     for (int i = 0; i < 6; ++i) {
         if (F.job_off[i + 1] <= F.job_off[i]) continue;
         const unsigned nj = (unsigned)(F.job_off[i + 1] - F.job_off[i]);
-        if (i == 5 && ctx->fir8p > 0) {
+        if (i == 5 && ctx->sw.fir8p > 0) {
             // persistent: one workgroup per CU (at most one per block), a multiple of the XCD
             // count.  Long outputs (h_early: milliseconds per launch) leave one CU in eight
             // to the other streams' small kernels, which cannot start beside a k_fir8p
             // workgroup (its VGPRs fill the CU): C5 118.4 - 119.4 ms with 224 of 256 CUs
             // against 118.8 - 124.0 with all of them; C3 keeps every CU
-            const int cus = ctx->fir8p_cus > 0 ? std::min(ctx->fir8p_cus, ctx->n_cu)
+            const int cus = ctx->sw.fir8p_cus > 0 ? std::min(ctx->sw.fir8p_cus, ctx->n_cu)
                                                : (F.h_early ? ctx->n_cu - ctx->n_cu / 8 : ctx->n_cu);
             const unsigned grid = (unsigned)std::max(MSG_XCDS, (std::min((int)nj, cus) / MSG_XCDS) * MSG_XCDS);
             HIPCHK(ctx, fir8_counters(ctx, s));
             HIPCHK(ctx, launch_fir8p(nj, grid, s, ctx->prt.p, ctx->fir_jobs.p + F.job_off[i],
-                                     ctx->d_fir4tab, ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p, ctx->fir8_ctr.p,
+                                     ctx->d_fir4tab.p, ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p, ctx->fir8_ctr.p,
                                      F.n_ola > 0 ? ctx->events.p : nullptr, ctx->grain.p, ctx->fir_lo.p));
         } else if (i == 5)
-            HIPCHK(ctx, launch_fir8(nj, s, ctx->prt.p, ctx->fir_jobs.p + F.job_off[i], ctx->d_fir4tab, ctx->hspec.p,
+            HIPCHK(ctx, launch_fir8(nj, s, ctx->prt.p, ctx->fir_jobs.p + F.job_off[i], ctx->d_fir4tab.p, ctx->hspec.p,
                                     ctx->mono_a.p, ctx->mono_y.p));
-        else if (i == 4 && ctx->fir4)
-            HIPCHK(ctx, launch_fir4(16384, nj, s, ctx->prt.p, ctx->fir_jobs.p + F.job_off[i], ctx->d_fir4tab,
+        else if (i == 4 && ctx->sw.fir4)
+            HIPCHK(ctx, launch_fir4(16384, nj, s, ctx->prt.p, ctx->fir_jobs.p + F.job_off[i], ctx->d_fir4tab.p,
                                     ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p));
         else
             HIPCHK(ctx, launch_fir2(1024 << i, nj, s, ctx->prt.p, ctx->fir_jobs.p + F.job_off[i],
-                                    ctx->d_fir2tab[i], ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p));
+                                    ctx->d_fir2tab[i].p, ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p));
     }
     stage_mark(ctx, 9, s);
     // presets with fir_on == 0 in a mixed batch: copy a -> y
@@ -985,7 +985,8 @@ static int odd_chirp(msg_ctx* ctx, Batch& b, int64_t n, const double2** spec) {
     if (it == ctx->so_bp.end()) {
         // bound the cache (one entry per distinct odd length, for the
         // life of the process): drop least-recently-used spectra of earlier
-        // batches while the cache holds more than 1 GiB (hipFree waits for them)
+        // batches while the cache holds more than 1 GiB (erase frees the entry;
+        // the free waits for the batches that read it)
         auto bytes = [&]() {
             size_t n_bytes = 0;
             for (auto& kv : ctx->so_bp) n_bytes += kv.second.cap * sizeof(double2);
@@ -997,13 +998,12 @@ static int odd_chirp(msg_ctx* ctx, Batch& b, int64_t n, const double2** spec) {
             for (auto& kv : ctx->so_bp_use)
                 if (kv.second < oldest) { oldest = kv.second; victim = kv.first; }
             if (victim < 0) break;
-            ctx->so_bp[victim].release();
             ctx->so_bp.erase(victim);
             ctx->so_bp_use.erase(victim);
         }
         it = ctx->so_bp.emplace(n, DevBuf<double2>()).first;
-        HIPCHK(ctx, it->second.ensure(stereo_odd_len(n, ctx->so_row, ctx->so_col)));
-        HIPCHK(ctx, launch_stereo_odd_kernel(n, ctx->so_row, ctx->so_col, it->second.p, ctx->so_A.p, b.s));
+        HIPCHK(ctx, it->second.ensure(stereo_odd_len(n, ctx->sw.so_row, ctx->sw.so_col)));
+        HIPCHK(ctx, launch_stereo_odd_kernel(n, ctx->sw.so_row, ctx->sw.so_col, it->second.p, ctx->so_A.p, b.s));
     }
     ctx->so_bp_use[n] = ctx->batch_serial;
     *spec = it->second.p;
@@ -1021,7 +1021,7 @@ static int enqueue_stereo(msg_ctx* ctx, Batch& b) {
     sy.flag64 = S.on ? ctx->f64_flag.p : nullptr;
     sy.part = S.on ? ctx->st_part.p : nullptr;
     sy.stats = S.on ? ctx->f64_stats.p : nullptr;
-    sy.f64mode = S.on ? ctx->fir64 : 0;
+    sy.f64mode = S.on ? ctx->sw.fir64 : 0;
     HIPCHK(ctx, launch_stereo_max((unsigned)b.stiles, s, ctx->prt.p, ctx->st_begin.p, P, yb, ctx->maxbits.p, sy));
     if (S.on)   // the float64 FIR's predictor per preset, from the tiles' partial sums
         HIPCHK(ctx, launch_stereo_pred((unsigned)P, s, ctx->prt.p, ctx->st_begin.p, b.stiles, ctx->maxbits.p, sy));
@@ -1053,7 +1053,7 @@ static int enqueue_stereo(msg_ctx* ctx, Batch& b) {
         const double2* chirp = nullptr;
         if (const int rc = odd_chirp(ctx, b, n, &chirp)) return rc;
         const double w = std::min(std::max(b.presets[p].stereo_width, 0.0), 1.0);
-        HIPCHK(ctx, launch_stereo_odd(n, ctx->so_row, ctx->so_col, b.prt[p].dr, w, yb + b.prt[p].y_off, chirp, ctx->so_A.p,
+        HIPCHK(ctx, launch_stereo_odd(n, ctx->sw.so_row, ctx->sw.so_col, b.prt[p].dr, w, yb + b.prt[p].y_off, chirp, ctx->so_A.p,
                                       ctx->so_r2.p + b.prt[p].r2_off, s));
     }
     int odd_tmax = 0;
@@ -1077,21 +1077,21 @@ static int enqueue_stereo(msg_ctx* ctx, Batch& b) {
 // host_sum[0..7]: plan, records, pinned upload, then the splits plan sizes,
 // plan events + tap merge, preset records, event records, lists + buffers.
 static void host_clocks(msg_ctx* ctx, const Batch& b) {
-    if (!ctx->prof_batch) return;
+    if (!ctx->prof.batch) return;
     const auto h3 = Batch::hclock::now();
     auto ms = [](Batch::hclock::time_point a, Batch::hclock::time_point z) {
         return std::chrono::duration<double, std::milli>(z - a).count();
     };
-    ctx->host_sum[0] += ms(b.h0, b.h1);
-    ctx->host_sum[1] += ms(b.h1, b.h2);
-    ctx->host_sum[2] += ms(b.h2, h3);
-    ctx->host_sum[3] += ms(b.h0, b.hA);
-    ctx->host_sum[4] += ms(b.hA, b.h1);
-    ctx->host_sum[5] += ms(b.h1, b.hB);
-    ctx->host_sum[6] += ms(b.hB, b.hC);
-    ctx->host_sum[7] += ms(b.hC, b.h2);
-    ctx->ola_fir_sum += b.fir.n_ola;
-    ++ctx->host_cnt;
+    ctx->prof.host_sum[0] += ms(b.h0, b.h1);
+    ctx->prof.host_sum[1] += ms(b.h1, b.h2);
+    ctx->prof.host_sum[2] += ms(b.h2, h3);
+    ctx->prof.host_sum[3] += ms(b.h0, b.hA);
+    ctx->prof.host_sum[4] += ms(b.hA, b.h1);
+    ctx->prof.host_sum[5] += ms(b.h1, b.hB);
+    ctx->prof.host_sum[6] += ms(b.hB, b.hC);
+    ctx->prof.host_sum[7] += ms(b.hC, b.h2);
+    ctx->prof.ola_fir_sum += b.fir.n_ola;
+    ++ctx->prof.host_cnt;
 }
 
 // Host mirrors of the last batch (msg_last_*), written only on success.
