@@ -315,6 +315,10 @@ struct msg_ctx {
     // msg_resample: signal extents + tile bases, the tap table
     DevBuf<int64_t> rs_meta;
     DevBuf<float> rs_tab;
+    // msg_loudness / msg_loudness_gain: signal extents + tile bases, the rate's table
+    // (loudness.h), per-tile filter states, per-tile energy and peak
+    DevBuf<int64_t> ld_meta;
+    DevBuf<double> ld_tab, ld_state, ld_part;
     // odd-length stereo rotation (kernels_stereo_odd.h)
     std::map<int64_t, DevBuf<double2>> so_bp;  // chirp kernel spectra by n (float64), LRU-bounded
     std::map<int64_t, uint64_t> so_bp_use;     // batch serial of each entry's last use

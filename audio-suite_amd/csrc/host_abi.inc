@@ -1,5 +1,6 @@
 // host_abi.inc — the host-side entry points of the C ABI (include/msgpu.h): the
-// render plan (plan.h) and the NumPy stream primitives (nprng.h).  Included
+// render plan (plan.h), the NumPy stream primitives (nprng.h) and the loudness
+// measurement's host reference (loudness.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables.
@@ -20,6 +21,19 @@ int msg_plan_host(const msg_preset* preset, const double* bp_bank, const double*
     const bool er = (preset->flags & MSG_F_ER_CLOUD) != 0;
     msgplan::plan_events(*preset, bp_bank, kHostZig, ir_frag_len, 0, *info, events,
                          er ? er_off : nullptr, er ? er_gain : nullptr);
+    return MSG_OK;
+}
+
+// BS.1770-4 integrated loudness of one signal in host memory: the definition of
+// loudness.h as one sequential float64 loop (ld_host)
+int msg_loudness_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_loudness_rec* rec) {
+    static_assert(sizeof(LoudRec) == sizeof(msg_loudness_rec), "LoudRec is msg_loudness_rec");
+    if (!rec || n < 0 || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    if (!ld_rate_ok(sr)) return fail(nullptr, MSG_E_VALUE, "the sample rate must be a multiple of 10, at least 4000");
+    LoudRec r;
+    ld_host(x, channels, n, sr, &r);
+    std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }
 

@@ -1,7 +1,8 @@
 // host_san.cpp — host-only build of libmsgpu's host entry points for the
 // sanitizers (SURVEY §5 "race detection / sanitizers"): the render plan
 // (plan.h, msg_plan_host), the NumPy stream primitives (nprng.h, msg_rng_*) and
-// the render digest's host reference (digest.h, msg_digest_host)
+// the host references of the render digest (digest.h, msg_digest_host) and of the
+// loudness measurement (loudness.h, msg_loudness_host),
 // compiled by g++ with -fsanitize=address,undefined into
 // msgpu/libmsgpu_hostsan.so.  The device entry points are stubs that fail with
 // MSG_E_DEVICE, so the ctypes binding (_lib.py) loads this library unchanged
@@ -18,6 +19,7 @@
 #include "plan.h"
 #include "host_pool.h"
 #include "digest.h"
+#include "loudness.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -40,6 +42,7 @@ int64_t msg_sizeof(int32_t which) {
         case 1: return (int64_t)sizeof(msg_event);
         case 2: return (int64_t)sizeof(msg_plan_info);
         case 3: return (int64_t)sizeof(msg_digest_rec);
+        case 4: return (int64_t)sizeof(msg_loudness_rec);
         default: return -1;
     }
 }
@@ -72,6 +75,14 @@ int msg_digest(msg_ctx*, const float*, const int64_t*, const int64_t*, int32_t, 
 }
 int msg_resample(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, const double*,
                  int64_t, float*, const int64_t*, void*) {
+    return no_device();
+}
+int msg_loudness(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, msg_loudness_rec*,
+                 void*) {
+    return no_device();
+}
+int msg_loudness_gain(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, msg_loudness_rec*, double,
+                      double, void*) {
     return no_device();
 }
 // the digest's host reference (digest.h), the same code the product library runs

@@ -186,3 +186,13 @@ void digest_host(const float* x, int64_t frames, void* rec);
 // first tiles), tab the plan's tap table (rs_table)
 hipError_t launch_resample(const RsPlan& p, int channels, unsigned tiles, hipStream_t s, const float* x, float* y,
                            const int64_t* meta, int n_sig, const float* tab, int up, int down, int64_t K);
+
+// BS.1770 integrated loudness (kernels_loudness.h): two sweeps over the tiles with the
+// tile scan between them, then one wave per signal into rec (msg_loudness_rec records).
+// meta: three int64 rows (offsets, frames, n_sig + 1 first tiles); tab: ld_table of the
+// rate; state: 4 * channels doubles per tile; part: 2 doubles per tile (energy, peak)
+hipError_t launch_loudness(int n_sig, int channels, unsigned tiles, hipStream_t s, const float* x, const int64_t* meta,
+                           int64_t hop, const double* tab, double* state, double* part, void* rec);
+// x *= (float)g per signal, g from its record; meta as above with tiles of LD_GAIN_TILE frames
+hipError_t launch_loudness_gain(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
+                                void* rec, double target, double ceiling);

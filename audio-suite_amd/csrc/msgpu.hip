@@ -31,6 +31,7 @@
 #include "fft_lds.h"
 #include "kernels_core.h"
 #include "launch.h"
+#include "loudness.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"
@@ -388,6 +389,24 @@ static int sf_upload(msg_ctx* ctx, hipStream_t s, const std::vector<PresetRt>& p
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
+// rows of a loudness call's metadata: offsets, frames, then n + 1 first tiles
+// (tiles_of(frames) per signal); returns the tile count, or -1 on a bad extent
+template <class F>
+static int64_t loud_meta(const int64_t* offsets, const int64_t* n, int32_t n_signals, F tiles_of,
+                         std::vector<int64_t>& meta) {
+    meta.assign((size_t)3 * n_signals + 1, 0);
+    int64_t tiles = 0;
+    for (int i = 0; i < n_signals; ++i) {
+        if (n[i] < 0 || n[i] > MSG_MAX_FRAMES || offsets[i] < 0) return -1;
+        meta[i] = offsets[i];
+        meta[(size_t)n_signals + i] = n[i];
+        meta[(size_t)2 * n_signals + i] = tiles;
+        tiles += tiles_of(n[i]);
+    }
+    meta[(size_t)3 * n_signals] = tiles;
+    return tiles;
+}
+
 extern "C" {
 
 int msg_abi_version(void) { return MSG_ABI_VERSION; }
@@ -400,6 +419,7 @@ int64_t msg_sizeof(int32_t which) {
         case 1: return (int64_t)sizeof(msg_event);
         case 2: return (int64_t)sizeof(msg_plan_info);
         case 3: return (int64_t)sizeof(msg_digest_rec);
+        case 4: return (int64_t)sizeof(msg_loudness_rec);
         default: return -1;
     }
 }
@@ -820,6 +840,65 @@ int msg_resample(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64
     HIPCHK(ctx, hipMemcpyAsync(ctx->rs_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, s));
     HIPCHK(ctx, launch_resample(plan, channels, (unsigned)tiles, s, x_dev, y_dev, ctx->rs_meta.p, n_signals,
                                 ctx->rs_tab.p, up, down, K));
+    HIPCHK(ctx, done.finish());
+    return MSG_OK;
+}
+
+int msg_loudness(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                 int32_t n_signals, int32_t sr, msg_loudness_rec* rec_dev, void* stream) {
+    if (!ctx || !offsets || !n || !rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
+    if (!ld_rate_ok(sr)) return fail(ctx, MSG_E_VALUE, "the sample rate must be a multiple of 10, at least 4000");
+    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
+        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    const int64_t hop = sr / 10;
+    std::vector<int64_t> meta;
+    const int64_t tiles = loud_meta(offsets, n, n_signals, [hop](int64_t f) { return ld_tiles(f, hop); }, meta);
+    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
+    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many loudness tiles");
+    if (tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    std::vector<double> tab(LD_TAB_N);
+    ld_table(sr, tab.data());
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, stream_handover(ctx, s));
+    DoneGuard done(ctx, s);
+    HIPCHK(ctx, ctx->ld_meta.ensure(meta.size()));
+    HIPCHK(ctx, ctx->ld_tab.ensure(tab.size()));
+    HIPCHK(ctx, ctx->ld_state.ensure((size_t)std::max<int64_t>(1, tiles) * 4 * channels));
+    HIPCHK(ctx, ctx->ld_part.ensure((size_t)std::max<int64_t>(1, tiles) * 2));
+    // pageable sources are staged before hipMemcpyAsync returns (as msg_fir's uploads)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ld_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ld_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, launch_loudness(n_signals, channels, (unsigned)tiles, s, x_dev, ctx->ld_meta.p, hop, ctx->ld_tab.p,
+                                ctx->ld_state.p, ctx->ld_part.p, rec_dev));
+    HIPCHK(ctx, done.finish());
+    return MSG_OK;
+}
+
+int msg_loudness_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                      int32_t n_signals, msg_loudness_rec* rec_dev, double target_lufs, double ceiling, void* stream) {
+    if (!ctx || !offsets || !n || !rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
+    if (!std::isfinite(target_lufs) || std::isnan(ceiling)) return fail(ctx, MSG_E_VALUE, "target and ceiling must be numbers");
+    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
+        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    std::vector<int64_t> meta;
+    const int64_t tiles = loud_meta(offsets, n, n_signals,
+                                    [](int64_t f) { return (f + LD_GAIN_TILE - 1) / LD_GAIN_TILE; }, meta);
+    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
+    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many gain tiles");
+    if (tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, stream_handover(ctx, s));
+    DoneGuard done(ctx, s);
+    HIPCHK(ctx, ctx->ld_meta.ensure(meta.size()));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ld_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, launch_loudness_gain(n_signals, channels, (unsigned)tiles, s, x_dev, ctx->ld_meta.p, rec_dev, target_lufs,
+                                     ceiling));
     HIPCHK(ctx, done.finish());
     return MSG_OK;
 }

@@ -13,6 +13,7 @@ from .params import DEFAULTS, CONFIGS, config_params, merged  # noqa: F401
 # from the function below to the module (reach the module's names with
 # ``from msgpu.resample import design, ...``)
 from . import resample as _resample  # noqa: F401
+from . import loudness as _loudness  # noqa: F401  (the same for ``msgpu.loudness``)
 
 
 def render(params, progress=None, device: int = 0):
@@ -20,7 +21,8 @@ def render(params, progress=None, device: int = 0):
     return _render(params, progress, device)
 
 
-def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None):
+def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
+                 out_lufs=None, out_ceiling=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -28,15 +30,22 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     tensors on one GPU, multi.DeviceResult handles across several).
     ``out_sr``: deliver "audio" / "device" results at that rate, resampled in HBM
     before any copy (resample.py; one device only); ``out_peak``: None, "preset"
-    or a number, the peak each resampled render is rescaled to."""
+    or a number, the peak each resampled render is rescaled to.  ``out_lufs``:
+    deliver each render at that BS.1770 integrated loudness (LUFS), measured at the
+    delivered rate and scaled in HBM (loudness.py; one device only), with
+    ``out_ceiling`` a linear sample peak it may not exceed."""
     if devices is not None and len(list(devices)) > 1:
         if out_sr is not None or out_peak is not None:
             raise NotImplementedError("out_sr on more than one device (multi.py sizes its shared memory by out_n)")
+        if out_lufs is not None or out_ceiling is not None:
+            raise NotImplementedError("out_lufs on more than one device")
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)
     if devices is not None:
         device = int(list(devices)[0])
     from .dropin import render_batch as _rb
+    if out_lufs is not None or out_ceiling is not None:
+        return _rb(params_list, device, results, out_sr, out_peak, out_lufs, out_ceiling)
     if out_sr is None and out_peak is None:
         return _rb(params_list, device, results)
     return _rb(params_list, device, results, out_sr, out_peak)
@@ -75,9 +84,17 @@ def resample(x, sr_in, sr_out, device: int = 0, **design):
     return _resample.resample(x, sr_in, sr_out, device, **design)
 
 
+def loudness(x, sr, device: int = 0):
+    """BS.1770-4 integrated loudness of x, (n,) or (n, 2), at sr Hz, measured on the device
+    in float64 (see loudness.py).  NumPy in, a float (LUFS) out; a device tensor in, a
+    one-element device tensor out with no host synchronise."""
+    return _loudness.loudness(x, sr, device)
+
+
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0, devices=None, **kw):
     """The app's batch render (on_batch, MS:1524-1596); see batch.py.  ``devices``
     shards the variants across GPUs as render_batch does; ``export_sr`` /
-    ``export_peak`` deliver the variants at another sample rate (one device)."""
+    ``export_peak`` deliver the variants at another sample rate, ``export_lufs`` /
+    ``export_ceiling`` at a BS.1770 integrated loudness (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

@@ -81,6 +81,11 @@ class MsgDigestRec(C.Structure):
                 ("h0", C.c_uint64), ("h1", C.c_uint64)]
 
 
+class MsgLoudnessRec(C.Structure):
+    _fields_ = [("lufs", C.c_double), ("mean_sq", C.c_double), ("peak", C.c_double), ("gain", C.c_double),
+                ("n_blocks", C.c_int32), ("n_kept", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -119,6 +124,11 @@ _PROTOS = {
     "msg_digest": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                              C.c_void_p, C.c_void_p]),
     "msg_digest_host": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(MsgDigestRec)]),
+    "msg_loudness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                               C.c_int32, C.c_void_p, C.c_void_p]),
+    "msg_loudness_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
+    "msg_loudness_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
@@ -155,7 +165,7 @@ def lib() -> C.CDLL:
                 f.argtypes = args
             if L.msg_abi_version() != ABI_VERSION:
                 raise RuntimeError("libmsgpu ABI version mismatch")
-            for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec)):
+            for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec, MsgLoudnessRec)):
                 if L.msg_sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmsgpu struct {st.__name__} size mismatch: "
                                        f"{L.msg_sizeof(which)} != {C.sizeof(st)}")

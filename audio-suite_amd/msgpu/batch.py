@@ -129,7 +129,8 @@ def _chunks(items, frames_of):
 
 
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0,
-                      names="wav", progress=None, devices=None, export_sr=None, export_peak=None):
+                      names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
+                      export_lufs=None, export_ceiling=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -143,6 +144,12 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     ``export_peak="preset"`` rescales each resampled variant so that max|y| is the
     preset's ``peak`` again (resampling moves the peak); None leaves the samples
     as resampled.  One device only.
+
+    ``export_lufs``: deliver every variant at that BS.1770-4 integrated loudness
+    (LUFS; -23 for EBU R 128): each is measured at the rate it is delivered at
+    (after the resampling when ``export_sr`` is given) and scaled in HBM before the
+    copy (loudness.py); ``export_ceiling``: a linear sample peak no scaled variant
+    may exceed (None: no limit).  Not together with ``export_peak``.  One device only.
     """
     from .pack import PackedBatch, out_frames
 
@@ -150,8 +157,14 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
         raise ValueError("export_peak needs export_sr")
     if export_peak not in (None, "preset"):
         raise ValueError("export_peak must be None or 'preset'")
+    if export_lufs is not None and export_peak is not None:
+        raise ValueError("export_lufs and export_peak are two level rules: give one")
+    if export_lufs is None and export_ceiling is not None:
+        raise ValueError("export_ceiling needs export_lufs")
     if export_sr is not None and devices is not None and len(list(devices)) > 1:
         raise NotImplementedError("export_sr on more than one device (multi.py sizes its shared memory by out_n)")
+    if export_lufs is not None and devices is not None and len(list(devices)) > 1:
+        raise NotImplementedError("export_lufs on more than one device")
     base = merged(base_params)
     pairs = variants(base, seeds, unfolds, stretches)
     keys = [key for key, _ in pairs]
@@ -186,6 +199,9 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
             from .dropin import resample_packed
             peaks = [float(base["peak"])] * len(chunk) if export_peak == "preset" else None
             out, offsets, lens = resample_packed(eng, out, offsets, lens, [base_sr] * len(chunk), out_sr, peaks)
+        if export_lufs is not None:                  # measured at the delivered rate, scaled where it lies
+            from .dropin import loudness_packed
+            loudness_packed(eng, out, offsets, lens, [out_sr] * len(chunk), export_lufs, export_ceiling)
         eng.torch.cuda.synchronize(eng.device)
         host = out.cpu().numpy()
         for key, off, n in zip(chunk, offsets, lens):

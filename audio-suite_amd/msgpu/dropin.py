@@ -121,6 +121,28 @@ def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
     return y, y_off, y_lens
 
 
+def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None):
+    """Bring renders lying in a device tensor ((frames, 2) float32, render i at frame
+    offsets[i] with lens[i] frames at rates[i] Hz) to ``target_lufs`` where they lie:
+    msg_loudness then msg_loudness_gain per distinct rate, the gain formed on the
+    device from each render's record (no host synchronise).  ``ceiling``: a linear
+    sample peak no render may exceed (None: no limit).  Scales y in place and returns
+    the device records in render order (engine.Engine.loudness)."""
+    torch = eng.torch
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rates = [int(s) for s in rates]
+    rec = torch.empty((len(rates), 5), dtype=torch.float64, device=y.device)
+    for rate in sorted(set(rates)):
+        idx = [i for i, s in enumerate(rates) if s == rate]
+        r = eng.loudness(y, offsets[idx], lens[idx], 2, rate)
+        eng.loudness_gain(y, offsets[idx], lens[idx], 2, r, float(target_lufs), ceiling)
+        if len(idx) == len(rates):
+            return r
+        rec[torch.as_tensor(idx, device=y.device)] = r
+    return rec
+
+
 def _out_peaks(params_list, out_peak):
     if out_peak is None:
         return None
@@ -131,27 +153,42 @@ def _out_peaks(params_list, out_peak):
     return [float(out_peak)] * len(params_list)
 
 
-def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None):
+def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
+                 out_ceiling=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
     ``out_sr``: deliver the renders at that rate, resampled in HBM before any copy
     ("audio" or "device"); ``out_peak``: None, "preset" or a number, the peak the
-    resampled renders are rescaled to (resample_packed)."""
+    resampled renders are rescaled to (resample_packed).  ``out_lufs``: deliver each
+    render at that BS.1770 integrated loudness, measured at the rate it is delivered at
+    and scaled in HBM (loudness_packed); ``out_ceiling``: a linear sample peak the scaled
+    renders may not exceed."""
     if results not in ("audio", "stats", "device"):
         raise ValueError("results must be 'audio', 'stats' or 'device'")
     if out_sr is None and out_peak is not None:
         raise ValueError("out_peak needs out_sr")
     if out_sr is not None and results == "stats":
         raise ValueError("out_sr applies to results 'audio' or 'device'")
+    if out_lufs is not None and out_peak is not None:
+        raise ValueError("out_lufs and out_peak are two level rules: give one")
+    if out_lufs is not None and results == "stats":
+        raise ValueError("out_lufs applies to results 'audio' or 'device'")
+    if out_lufs is None and out_ceiling is not None:
+        raise ValueError("out_ceiling needs out_lufs")
     params_list = list(params_list)
     eng = default_engine(device)
     packed = PackedBatch(params_list)
     out = eng.render_packed(packed)
+    if out_lufs is not None and out_sr is None:
+        loudness_packed(eng, out, packed.offsets, packed.out_n, [merged(p)["base_sr"] for p in params_list],
+                        out_lufs, out_ceiling)
     if out_sr is not None:
         y, y_off, y_lens = resample_packed(eng, out, packed.offsets, packed.out_n,
                                            [merged(p)["base_sr"] for p in params_list], int(out_sr),
                                            _out_peaks(params_list, out_peak))
+        if out_lufs is not None:
+            loudness_packed(eng, y, y_off, y_lens, [int(out_sr)] * len(params_list), out_lufs, out_ceiling)
         parts = [y[int(o):int(o) + int(n)] for o, n in zip(y_off, y_lens)]
         if results == "device":
             return parts

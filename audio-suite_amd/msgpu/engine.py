@@ -222,6 +222,68 @@ class Engine:
             host = rec.cpu().numpy()       # ordered after the digest on its stream
         return host[:n].copy().view(DIGEST_DTYPE).reshape(n)
 
+    def _signals(self, x, offsets, lens, channels):
+        torch = self.torch
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device.type != "cuda":
+            raise ValueError("x must be a contiguous float32 device tensor")
+        channels = int(channels)
+        if channels not in (1, 2):
+            raise ValueError("channels must be 1 or 2")
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        cnt = np.ascontiguousarray(lens, dtype=np.int64)
+        if off.shape != cnt.shape or off.ndim != 1:
+            raise ValueError("offsets and lens must be 1-D of one length")
+        if off.size and (int(off.min()) < 0 or int(cnt.min()) < 0 or
+                         int((off + cnt).max()) * channels > x.numel()):
+            raise ValueError("a signal extends past the input tensor")
+        return channels, off, cnt
+
+    def loudness(self, x, offsets, lens, channels, sr, stream=None):
+        """msg_loudness of signals lying in a device float32 tensor (mono samples or
+        interleaved L/R frames, signal i at frame offsets[i] with lens[i] frames at sr
+        Hz): BS.1770-4 integrated loudness, reduced on the device in float64.
+        Returns the device records, a float64 tensor (signals, 5) whose rows are
+        msg_loudness_rec (lufs, mean_sq, peak, gain, then n_blocks and n_kept as two
+        int32; loudness.records reads them on the host), enqueued on ``stream``."""
+        torch = self.torch
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        sr = int(sr)
+        if sr < 4000 or sr % 10:
+            raise ValueError("the sample rate must be a multiple of 10, at least 4000")
+        n = int(off.size)
+        rec = torch.empty((n, 5), dtype=torch.float64, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        with self._lock:
+            L.check(L.lib().msg_loudness(self._ctx, C.c_void_p(x.data_ptr()), channels,
+                                         off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), n, sr,
+                                         C.c_void_p(rec.data_ptr()), C.c_void_p(stream.cuda_stream)), self._ctx)
+        return rec
+
+    def loudness_gain(self, x, offsets, lens, channels, rec, target_lufs, ceiling=None, stream=None):
+        """msg_loudness_gain: scale each signal of x in place to ``target_lufs`` from its
+        device record (Engine.loudness), the gain formed on the device; ``ceiling``: a
+        linear sample peak no scaled signal may exceed (None: no limit).  Writes the
+        gains into ``rec`` and returns it; enqueued on ``stream``, no host synchronise."""
+        torch = self.torch
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        n = int(off.size)
+        if rec.dtype != torch.float64 or not rec.is_contiguous() or rec.device != x.device or rec.numel() < 5 * n:
+            raise ValueError("rec must be the float64 record tensor of Engine.loudness on x's device")
+        ceil = 0.0 if ceiling is None else float(ceiling)
+        if ceiling is not None and not ceil > 0.0:
+            raise ValueError("the ceiling must be positive")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        with self._lock:
+            L.check(L.lib().msg_loudness_gain(self._ctx, C.c_void_p(x.data_ptr()), channels,
+                                              off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              cnt.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                              C.c_void_p(rec.data_ptr()), float(target_lufs), ceil,
+                                              C.c_void_p(stream.cuda_stream)), self._ctx)
+        return rec
+
     # ---- last-batch inspection -----------------------------------------
     def last_plan(self):
         arr = (L.MsgPlanInfo * self._last_n)()

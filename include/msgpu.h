@@ -14,6 +14,7 @@
  *   msg_plan_host    the render's scalar/RNG plan, host-side    (MS:589-646, 742-751)
  *   msg_digest       per-render checksums on the device         (MS:1585-1589)
  *   msg_resample     sample-rate conversion of renders in HBM     (no counterpart: SURVEY §0)
+ *   msg_loudness     BS.1770 integrated loudness and LUFS gain in HBM (no counterpart)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
 #ifndef MSGPU_H
@@ -114,7 +115,8 @@ int         msg_abi_version(void);
 /* Threads of the process-wide host planning pool (the caller included):
  * MSGPU_HOST_THREADS, else the CPU affinity / LOCAL_WORLD_SIZE, at most 16. */
 int         msg_host_threads(void);
-/* sizeof of the ABI structs (0 msg_preset, 1 msg_event, 2 msg_plan_info, 3 msg_digest_rec) for binding checks */
+/* sizeof of the ABI structs (0 msg_preset, 1 msg_event, 2 msg_plan_info, 3 msg_digest_rec,
+ * 4 msg_loudness_rec) for binding checks */
 int64_t     msg_sizeof(int32_t which);
 msg_ctx*    msg_create(int device_ordinal);
 void        msg_destroy(msg_ctx* ctx);
@@ -260,6 +262,41 @@ int msg_digest(msg_ctx* ctx, const float* out_dev, const int64_t* out_offsets, c
                int32_t n_renders, msg_digest_rec* rec_dev, void* stream);
 /* The same record of one render in host memory (x: out_n interleaved frames). */
 int msg_digest_host(const float* x, int64_t out_n, msg_digest_rec* rec);
+
+/* ITU-R BS.1770-4 integrated loudness of signals lying in HBM (csrc/loudness.h holds
+ * the definition, DESIGN.md "Loudness" the kernels): K-weighting designed for the
+ * rate sr (sr % 10 == 0, else MSG_E_VALUE), 400 ms blocks at 75 % overlap (complete
+ * blocks only), the absolute gate at -70 LUFS and the relative gate 10 LU under the
+ * mean of the blocks above it, all in float64 on float32 samples.
+ *   lufs      integrated loudness, -inf when no block survives the gates
+ *   mean_sq   mean of the kept blocks' z (lufs = -0.691 + 10 log10 mean_sq), else 0
+ *   peak      sample peak max |x| over every frame and channel
+ *   gain      0 until msg_loudness_gain writes the gain it applied
+ *   n_blocks  complete blocks,  n_kept  blocks that pass both gates
+ * A signal's record does not depend on the batch it is measured in, and a
+ * repeated call gives the same bits. */
+typedef struct msg_loudness_rec {
+    double lufs, mean_sq, peak, gain;
+    int32_t n_blocks, n_kept;
+} msg_loudness_rec;
+/* x_dev: mono (channels = 1) or interleaved L/R (channels = 2) float32 signals in one
+ * device buffer, signal i at frame offsets[i] with n[i] frames (host arrays; mono
+ * signals may start at any float, x_dev of stereo signals is 8-byte aligned);
+ * rec_dev: n_signals device records.  Enqueued on stream; one call in flight per
+ * context. */
+int msg_loudness(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                 int32_t n_signals, int32_t sr, msg_loudness_rec* rec_dev, void* stream);
+/* Scale each signal in place by (float)g, g formed on the device from its record:
+ *   g = 10^((target_lufs - lufs) / 20);  ceiling > 0 and g peak > ceiling: g = ceiling / peak;
+ *   lufs = -inf: g = 1 (a silent signal stays as it is).
+ * Writes g to rec.gain; the record's other fields keep the values measured before
+ * the scaling.  The signals must not overlap.  Enqueued on stream: no host
+ * synchronise between msg_loudness and this call. */
+int msg_loudness_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                      int32_t n_signals, msg_loudness_rec* rec_dev, double target_lufs, double ceiling, void* stream);
+/* The same definition as a sequential float64 loop over one signal in host memory
+ * (x: n frames of `channels` interleaved words); needs no device. */
+int msg_loudness_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_loudness_rec* rec);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
