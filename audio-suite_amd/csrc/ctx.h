@@ -319,6 +319,11 @@ struct msg_ctx {
     // (loudness.h), per-tile filter states, per-tile energy and peak
     DevBuf<int64_t> ld_meta;
     DevBuf<double> ld_tab, ld_state, ld_part;
+    // msg_truepeak / msg_truepeak_gain: the interpolator's taps (truepeak.h, uploaded once
+    // by msg_create), signal extents + tile bases, per-tile maxima
+    DevBuf<float> d_tp_tab;
+    DevBuf<int64_t> tp_meta;
+    DevBuf<uint2> tp_part;
     // odd-length stereo rotation (kernels_stereo_odd.h)
     std::map<int64_t, DevBuf<double2>> so_bp;  // chirp kernel spectra by n (float64), LRU-bounded
     std::map<int64_t, uint64_t> so_bp_use;     // batch serial of each entry's last use

@@ -1,6 +1,6 @@
 // host_abi.inc — the host-side entry points of the C ABI (include/msgpu.h): the
-// render plan (plan.h), the NumPy stream primitives (nprng.h) and the loudness
-// measurement's host reference (loudness.h).  Included
+// render plan (plan.h), the NumPy stream primitives (nprng.h) and the host references
+// of the loudness and true-peak measurements (loudness.h, truepeak.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables.
@@ -33,6 +33,19 @@ int msg_loudness_host(const float* x, int32_t channels, int64_t n, int32_t sr, m
     if (!ld_rate_ok(sr)) return fail(nullptr, MSG_E_VALUE, "the sample rate must be a multiple of 10, at least 4000");
     LoudRec r;
     ld_host(x, channels, n, sr, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// BS.1770-4 true peak of one signal in host memory: the definition of truepeak.h as
+// one loop (tp_host), the float32 arithmetic and the record of the device to the bit
+int msg_truepeak_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_truepeak_rec* rec) {
+    static_assert(sizeof(TruePeakRec) == sizeof(msg_truepeak_rec), "TruePeakRec is msg_truepeak_rec");
+    if (!rec || n < 0 || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    if (sr < 1) return fail(nullptr, MSG_E_VALUE, "the sample rate must be positive");
+    TruePeakRec r;
+    tp_host(x, channels, n, sr, &r);
     std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }

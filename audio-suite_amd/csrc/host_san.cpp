@@ -2,7 +2,8 @@
 // sanitizers (SURVEY §5 "race detection / sanitizers"): the render plan
 // (plan.h, msg_plan_host), the NumPy stream primitives (nprng.h, msg_rng_*) and
 // the host references of the render digest (digest.h, msg_digest_host) and of the
-// loudness measurement (loudness.h, msg_loudness_host),
+// loudness and true-peak measurements (loudness.h, msg_loudness_host; truepeak.h,
+// msg_truepeak_host),
 // compiled by g++ with -fsanitize=address,undefined into
 // msgpu/libmsgpu_hostsan.so.  The device entry points are stubs that fail with
 // MSG_E_DEVICE, so the ctypes binding (_lib.py) loads this library unchanged
@@ -20,6 +21,7 @@
 #include "host_pool.h"
 #include "digest.h"
 #include "loudness.h"
+#include "truepeak.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -43,6 +45,7 @@ int64_t msg_sizeof(int32_t which) {
         case 2: return (int64_t)sizeof(msg_plan_info);
         case 3: return (int64_t)sizeof(msg_digest_rec);
         case 4: return (int64_t)sizeof(msg_loudness_rec);
+        case 5: return (int64_t)sizeof(msg_truepeak_rec);
         default: return -1;
     }
 }
@@ -83,6 +86,14 @@ int msg_loudness(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*
 }
 int msg_loudness_gain(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, msg_loudness_rec*, double,
                       double, void*) {
+    return no_device();
+}
+int msg_truepeak(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, msg_truepeak_rec*,
+                 void*) {
+    return no_device();
+}
+int msg_truepeak_gain(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, msg_loudness_rec*,
+                      msg_truepeak_rec*, double, double, double, void*) {
     return no_device();
 }
 // the digest's host reference (digest.h), the same code the product library runs

@@ -196,3 +196,12 @@ hipError_t launch_loudness(int n_sig, int channels, unsigned tiles, hipStream_t 
 // x *= (float)g per signal, g from its record; meta as above with tiles of LD_GAIN_TILE frames
 hipError_t launch_loudness_gain(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
                                 void* rec, double target, double ceiling);
+
+// BS.1770 true peak (kernels_truepeak.h): one workgroup per tile of TP_TILE positions, then
+// one wave per signal into rec (msg_truepeak_rec records).  meta as for the loudness
+// (tiles: tp_tiles); tab: tp_table, uploaded once with the context; part: one uint2 per tile
+hipError_t launch_truepeak(int n_sig, int channels, int os, unsigned tiles, hipStream_t s, const float* x,
+                           const int64_t* meta, const float* tab, void* part, void* rec);
+// x *= (float)g per signal, g from its records (loud_rec may be null); tiles of TP_GAIN_TILE frames
+hipError_t launch_truepeak_gain(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
+                                void* loud_rec, void* tp_rec, double target, double ceil_tp, double ceil_pk);

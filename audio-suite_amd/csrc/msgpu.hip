@@ -32,6 +32,7 @@
 #include "kernels_core.h"
 #include "launch.h"
 #include "loudness.h"
+#include "truepeak.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"
@@ -420,6 +421,7 @@ int64_t msg_sizeof(int32_t which) {
         case 2: return (int64_t)sizeof(msg_plan_info);
         case 3: return (int64_t)sizeof(msg_digest_rec);
         case 4: return (int64_t)sizeof(msg_loudness_rec);
+        case 5: return (int64_t)sizeof(msg_truepeak_rec);
         default: return -1;
     }
 }
@@ -482,6 +484,11 @@ msg_ctx* msg_create(int device_ordinal) {
     if (!up2(ctx->d_spec3_tab, spec3_tables(tab), tab)) {
         g_err = "uploading spectral twiddle tables failed";
         return nullptr;
+    }
+    {
+        float tp_tab[TP_TAB_N];
+        tp_table(tp_tab);
+        if (!up(ctx->d_tp_tab, tp_tab, (size_t)TP_TAB_N)) { g_err = "uploading the true-peak taps failed"; return nullptr; }
     }
     int cu = 0;
     if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cu >= MSG_XCDS)
@@ -899,6 +906,61 @@ int msg_loudness_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_
     HIPCHK(ctx, hipMemcpyAsync(ctx->ld_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
     HIPCHK(ctx, launch_loudness_gain(n_signals, channels, (unsigned)tiles, s, x_dev, ctx->ld_meta.p, rec_dev, target_lufs,
                                      ceiling));
+    HIPCHK(ctx, done.finish());
+    return MSG_OK;
+}
+
+int msg_truepeak(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                 int32_t n_signals, int32_t sr, msg_truepeak_rec* rec_dev, void* stream) {
+    if (!ctx || !offsets || !n || !rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
+    if (sr < 1) return fail(ctx, MSG_E_VALUE, "the sample rate must be positive");
+    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
+        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    std::vector<int64_t> meta;
+    const int64_t tiles = loud_meta(offsets, n, n_signals, [](int64_t f) { return tp_tiles(f); }, meta);
+    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
+    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many true-peak tiles");
+    if (tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, stream_handover(ctx, s));
+    DoneGuard done(ctx, s);
+    HIPCHK(ctx, ctx->tp_meta.ensure(meta.size()));
+    HIPCHK(ctx, ctx->tp_part.ensure((size_t)std::max<int64_t>(1, tiles)));
+    // a pageable source is staged before hipMemcpyAsync returns (as msg_fir's uploads)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->tp_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, launch_truepeak(n_signals, channels, tp_os(sr), (unsigned)tiles, s, x_dev, ctx->tp_meta.p,
+                                ctx->d_tp_tab.p, ctx->tp_part.p, rec_dev));
+    HIPCHK(ctx, done.finish());
+    return MSG_OK;
+}
+
+int msg_truepeak_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                      int32_t n_signals, msg_loudness_rec* loud_rec_dev, msg_truepeak_rec* tp_rec_dev,
+                      double target_lufs, double ceiling_tp, double ceiling_peak, void* stream) {
+    if (!ctx || !offsets || !n || !tp_rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
+    if ((loud_rec_dev && !std::isfinite(target_lufs)) || std::isnan(ceiling_tp) || std::isnan(ceiling_peak))
+        return fail(ctx, MSG_E_VALUE, "target and ceilings must be numbers");
+    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
+        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    std::vector<int64_t> meta;
+    const int64_t tiles = loud_meta(offsets, n, n_signals,
+                                    [](int64_t f) { return (f + TP_GAIN_TILE - 1) / TP_GAIN_TILE; }, meta);
+    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
+    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many gain tiles");
+    if (tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, stream_handover(ctx, s));
+    DoneGuard done(ctx, s);
+    HIPCHK(ctx, ctx->tp_meta.ensure(meta.size()));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->tp_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, launch_truepeak_gain(n_signals, channels, (unsigned)tiles, s, x_dev, ctx->tp_meta.p, loud_rec_dev,
+                                     tp_rec_dev, loud_rec_dev ? target_lufs : 0.0, ceiling_tp, ceiling_peak));
     HIPCHK(ctx, done.finish());
     return MSG_OK;
 }

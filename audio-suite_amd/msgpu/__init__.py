@@ -14,6 +14,7 @@ from .params import DEFAULTS, CONFIGS, config_params, merged  # noqa: F401
 # ``from msgpu.resample import design, ...``)
 from . import resample as _resample  # noqa: F401
 from . import loudness as _loudness  # noqa: F401  (the same for ``msgpu.loudness``)
+from . import truepeak as _truepeak  # noqa: F401
 
 
 def render(params, progress=None, device: int = 0):
@@ -22,7 +23,7 @@ def render(params, progress=None, device: int = 0):
 
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
-                 out_lufs=None, out_ceiling=None):
+                 out_lufs=None, out_ceiling=None, out_true_peak=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -33,17 +34,23 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     or a number, the peak each resampled render is rescaled to.  ``out_lufs``:
     deliver each render at that BS.1770 integrated loudness (LUFS), measured at the
     delivered rate and scaled in HBM (loudness.py; one device only), with
-    ``out_ceiling`` a linear sample peak it may not exceed."""
+    ``out_ceiling`` a linear sample peak it may not exceed.  ``out_true_peak``: a
+    ceiling in dBTP (BS.1770 true peak at the delivered rate, truepeak.py; one device
+    only), alone or with ``out_lufs`` / ``out_ceiling``; not with ``out_peak``."""
     if devices is not None and len(list(devices)) > 1:
         if out_sr is not None or out_peak is not None:
             raise NotImplementedError("out_sr on more than one device (multi.py sizes its shared memory by out_n)")
         if out_lufs is not None or out_ceiling is not None:
             raise NotImplementedError("out_lufs on more than one device")
+        if out_true_peak is not None:
+            raise NotImplementedError("out_true_peak on more than one device")
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)
     if devices is not None:
         device = int(list(devices)[0])
     from .dropin import render_batch as _rb
+    if out_true_peak is not None:
+        return _rb(params_list, device, results, out_sr, out_peak, out_lufs, out_ceiling, out_true_peak)
     if out_lufs is not None or out_ceiling is not None:
         return _rb(params_list, device, results, out_sr, out_peak, out_lufs, out_ceiling)
     if out_sr is None and out_peak is None:
@@ -91,10 +98,18 @@ def loudness(x, sr, device: int = 0):
     return _loudness.loudness(x, sr, device)
 
 
+def true_peak(x, sr, device: int = 0, db: bool = False):
+    """BS.1770-4 true peak of x, (n,) or (n, 2), at sr Hz, measured on the device (see
+    truepeak.py): linear, or dBTP with ``db``.  NumPy in, a float out; a device tensor in,
+    a one-element device tensor out with no host synchronise."""
+    return _truepeak.true_peak(x, sr, device, db)
+
+
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0, devices=None, **kw):
     """The app's batch render (on_batch, MS:1524-1596); see batch.py.  ``devices``
     shards the variants across GPUs as render_batch does; ``export_sr`` /
     ``export_peak`` deliver the variants at another sample rate, ``export_lufs`` /
-    ``export_ceiling`` at a BS.1770 integrated loudness (one device)."""
+    ``export_ceiling`` at a BS.1770 integrated loudness, ``export_true_peak`` under a
+    ceiling in dBTP (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

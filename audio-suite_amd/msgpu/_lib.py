@@ -86,6 +86,11 @@ class MsgLoudnessRec(C.Structure):
                 ("n_blocks", C.c_int32), ("n_kept", C.c_int32)]
 
 
+class MsgTruePeakRec(C.Structure):
+    _fields_ = [("true_peak", C.c_double), ("peak", C.c_double), ("dbtp", C.c_double), ("gain", C.c_double),
+                ("os", C.c_int32), ("pad", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -129,6 +134,11 @@ _PROTOS = {
     "msg_loudness_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "msg_loudness_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "msg_truepeak": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                               C.c_int32, C.c_void_p, C.c_void_p]),
+    "msg_truepeak_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "msg_truepeak_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
@@ -165,7 +175,8 @@ def lib() -> C.CDLL:
                 f.argtypes = args
             if L.msg_abi_version() != ABI_VERSION:
                 raise RuntimeError("libmsgpu ABI version mismatch")
-            for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec, MsgLoudnessRec)):
+            for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec, MsgLoudnessRec,
+                                        MsgTruePeakRec)):
                 if L.msg_sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmsgpu struct {st.__name__} size mismatch: "
                                        f"{L.msg_sizeof(which)} != {C.sizeof(st)}")

@@ -130,7 +130,7 @@ def _chunks(items, frames_of):
 
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0,
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
-                      export_lufs=None, export_ceiling=None):
+                      export_lufs=None, export_ceiling=None, export_true_peak=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -150,6 +150,11 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     (after the resampling when ``export_sr`` is given) and scaled in HBM before the
     copy (loudness.py); ``export_ceiling``: a linear sample peak no scaled variant
     may exceed (None: no limit).  Not together with ``export_peak``.  One device only.
+
+    ``export_true_peak``: a ceiling in dBTP (-1 for EBU R 128) on every variant's
+    BS.1770-4 true peak, measured at the rate it is delivered at and held in HBM before
+    the copy (truepeak.py); alone, or with ``export_lufs`` / ``export_ceiling``, one
+    gain per variant from all of them.  Not together with ``export_peak``.  One device only.
     """
     from .pack import PackedBatch, out_frames
 
@@ -159,12 +164,16 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
         raise ValueError("export_peak must be None or 'preset'")
     if export_lufs is not None and export_peak is not None:
         raise ValueError("export_lufs and export_peak are two level rules: give one")
-    if export_lufs is None and export_ceiling is not None:
+    if export_true_peak is not None and export_peak is not None:
+        raise ValueError("export_true_peak and export_peak are two level rules: give one")
+    if export_lufs is None and export_true_peak is None and export_ceiling is not None:
         raise ValueError("export_ceiling needs export_lufs")
     if export_sr is not None and devices is not None and len(list(devices)) > 1:
         raise NotImplementedError("export_sr on more than one device (multi.py sizes its shared memory by out_n)")
     if export_lufs is not None and devices is not None and len(list(devices)) > 1:
         raise NotImplementedError("export_lufs on more than one device")
+    if export_true_peak is not None and devices is not None and len(list(devices)) > 1:
+        raise NotImplementedError("export_true_peak on more than one device")
     base = merged(base_params)
     pairs = variants(base, seeds, unfolds, stretches)
     keys = [key for key, _ in pairs]
@@ -201,7 +210,11 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
             out, offsets, lens = resample_packed(eng, out, offsets, lens, [base_sr] * len(chunk), out_sr, peaks)
         if export_lufs is not None:                  # measured at the delivered rate, scaled where it lies
             from .dropin import loudness_packed
-            loudness_packed(eng, out, offsets, lens, [out_sr] * len(chunk), export_lufs, export_ceiling)
+            loudness_packed(eng, out, offsets, lens, [out_sr] * len(chunk), export_lufs, export_ceiling,
+                            export_true_peak)
+        elif export_true_peak is not None:           # a ceiling alone
+            from .dropin import truepeak_packed
+            truepeak_packed(eng, out, offsets, lens, [out_sr] * len(chunk), export_true_peak, export_ceiling)
         eng.torch.cuda.synchronize(eng.device)
         host = out.cpu().numpy()
         for key, off, n in zip(chunk, offsets, lens):

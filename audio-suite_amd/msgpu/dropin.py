@@ -121,13 +121,15 @@ def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
     return y, y_off, y_lens
 
 
-def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None):
+def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None, true_peak=None):
     """Bring renders lying in a device tensor ((frames, 2) float32, render i at frame
     offsets[i] with lens[i] frames at rates[i] Hz) to ``target_lufs`` where they lie:
     msg_loudness then msg_loudness_gain per distinct rate, the gain formed on the
     device from each render's record (no host synchronise).  ``ceiling``: a linear
-    sample peak no render may exceed (None: no limit).  Scales y in place and returns
-    the device records in render order (engine.Engine.loudness)."""
+    sample peak no render may exceed (None: no limit).  ``true_peak``: a ceiling in
+    dBTP (BS.1770 true peak, truepeak.py) no render may exceed: msg_truepeak is
+    measured too and msg_truepeak_gain forms the one gain from both records.  Scales y
+    in place and returns the device records in render order (engine.Engine.loudness)."""
     torch = eng.torch
     offsets = np.asarray(offsets, dtype=np.int64)
     lens = np.asarray(lens, dtype=np.int64)
@@ -136,11 +138,51 @@ def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None):
     for rate in sorted(set(rates)):
         idx = [i for i, s in enumerate(rates) if s == rate]
         r = eng.loudness(y, offsets[idx], lens[idx], 2, rate)
-        eng.loudness_gain(y, offsets[idx], lens[idx], 2, r, float(target_lufs), ceiling)
+        if true_peak is None:
+            eng.loudness_gain(y, offsets[idx], lens[idx], 2, r, float(target_lufs), ceiling)
+        else:
+            t = eng.true_peak(y, offsets[idx], lens[idx], 2, rate)
+            eng.true_peak_gain(y, offsets[idx], lens[idx], 2, t, r, float(target_lufs), _dbtp(true_peak), ceiling)
         if len(idx) == len(rates):
             return r
         rec[torch.as_tensor(idx, device=y.device)] = r
     return rec
+
+
+def _dbtp(true_peak):
+    """A dBTP ceiling as a linear true peak."""
+    v = float(true_peak)
+    if not np.isfinite(v):
+        raise ValueError("the true-peak ceiling must be a number of dBTP")
+    return 10.0 ** (v / 20.0)
+
+
+def truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling=None):
+    """Hold renders lying in a device tensor (as loudness_packed) under ``true_peak`` dBTP
+    where they lie, with no loudness target: msg_truepeak then msg_truepeak_gain per
+    distinct rate, the gain (1 where the ceiling does not bind) formed on the device.
+    ``ceiling``: a linear sample peak as well (None: no limit).  Scales y in place and
+    returns the device records in render order (engine.Engine.true_peak)."""
+    torch = eng.torch
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rates = [int(s) for s in rates]
+    rec = torch.empty((len(rates), 5), dtype=torch.float64, device=y.device)
+    for rate in sorted(set(rates)):
+        idx = [i for i, s in enumerate(rates) if s == rate]
+        t = eng.true_peak(y, offsets[idx], lens[idx], 2, rate)
+        eng.true_peak_gain(y, offsets[idx], lens[idx], 2, t, None, None, _dbtp(true_peak), ceiling)
+        if len(idx) == len(rates):
+            return t
+        rec[torch.as_tensor(idx, device=y.device)] = t
+    return rec
+
+
+def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak):
+    if lufs is not None:
+        loudness_packed(eng, y, offsets, lens, rates, lufs, ceiling, true_peak)
+    elif true_peak is not None:
+        truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling)
 
 
 def _out_peaks(params_list, out_peak):
@@ -154,7 +196,7 @@ def _out_peaks(params_list, out_peak):
 
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
-                 out_ceiling=None):
+                 out_ceiling=None, out_true_peak=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -163,9 +205,15 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     resampled renders are rescaled to (resample_packed).  ``out_lufs``: deliver each
     render at that BS.1770 integrated loudness, measured at the rate it is delivered at
     and scaled in HBM (loudness_packed); ``out_ceiling``: a linear sample peak the scaled
-    renders may not exceed."""
+    renders may not exceed.  ``out_true_peak``: a ceiling in dBTP (BS.1770 true peak at
+    the delivered rate) they may not exceed, alone or with ``out_lufs`` / ``out_ceiling``
+    (truepeak_packed, loudness_packed)."""
     if results not in ("audio", "stats", "device"):
         raise ValueError("results must be 'audio', 'stats' or 'device'")
+    if out_true_peak is not None and out_peak is not None:
+        raise ValueError("out_true_peak and out_peak are two level rules: give one")
+    if out_true_peak is not None and results == "stats":
+        raise ValueError("out_true_peak applies to results 'audio' or 'device'")
     if out_sr is None and out_peak is not None:
         raise ValueError("out_peak needs out_sr")
     if out_sr is not None and results == "stats":
@@ -174,21 +222,20 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
         raise ValueError("out_lufs and out_peak are two level rules: give one")
     if out_lufs is not None and results == "stats":
         raise ValueError("out_lufs applies to results 'audio' or 'device'")
-    if out_lufs is None and out_ceiling is not None:
+    if out_lufs is None and out_true_peak is None and out_ceiling is not None:
         raise ValueError("out_ceiling needs out_lufs")
     params_list = list(params_list)
     eng = default_engine(device)
     packed = PackedBatch(params_list)
     out = eng.render_packed(packed)
-    if out_lufs is not None and out_sr is None:
-        loudness_packed(eng, out, packed.offsets, packed.out_n, [merged(p)["base_sr"] for p in params_list],
-                        out_lufs, out_ceiling)
+    if out_sr is None:
+        _level(eng, out, packed.offsets, packed.out_n, [merged(p)["base_sr"] for p in params_list],
+               out_lufs, out_ceiling, out_true_peak)
     if out_sr is not None:
         y, y_off, y_lens = resample_packed(eng, out, packed.offsets, packed.out_n,
                                            [merged(p)["base_sr"] for p in params_list], int(out_sr),
                                            _out_peaks(params_list, out_peak))
-        if out_lufs is not None:
-            loudness_packed(eng, y, y_off, y_lens, [int(out_sr)] * len(params_list), out_lufs, out_ceiling)
+        _level(eng, y, y_off, y_lens, [int(out_sr)] * len(params_list), out_lufs, out_ceiling, out_true_peak)
         parts = [y[int(o):int(o) + int(n)] for o, n in zip(y_off, y_lens)]
         if results == "device":
             return parts

@@ -284,6 +284,65 @@ class Engine:
                                               C.c_void_p(stream.cuda_stream)), self._ctx)
         return rec
 
+    def true_peak(self, x, offsets, lens, channels, sr, stream=None):
+        """msg_truepeak of signals lying in a device float32 tensor (as Engine.loudness):
+        the BS.1770-4 Annex 2 true peak at sr Hz.  Returns the device records, a float64
+        tensor (signals, 5) whose rows are msg_truepeak_rec (true_peak, peak, dbtp, gain,
+        then os and a pad as two int32; truepeak.records reads them on the host),
+        enqueued on ``stream``."""
+        torch = self.torch
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        sr = int(sr)
+        if sr < 1:
+            raise ValueError("the sample rate must be positive")
+        n = int(off.size)
+        rec = torch.empty((n, 5), dtype=torch.float64, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        with self._lock:
+            L.check(L.lib().msg_truepeak(self._ctx, C.c_void_p(x.data_ptr()), channels,
+                                         off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), n, sr,
+                                         C.c_void_p(rec.data_ptr()), C.c_void_p(stream.cuda_stream)), self._ctx)
+        return rec
+
+    def true_peak_gain(self, x, offsets, lens, channels, tp_rec, loud_rec=None, target_lufs=None, ceiling_tp=None,
+                       ceiling_peak=None, stream=None):
+        """msg_truepeak_gain: scale each signal of x in place from its device records, the
+        gain formed on the device: to ``target_lufs`` when ``loud_rec`` (Engine.loudness)
+        is given, then held under ``ceiling_tp``, a linear true peak, and ``ceiling_peak``,
+        a linear sample peak (None: no limit).  Writes the gains into ``tp_rec`` (and
+        ``loud_rec``) and returns ``tp_rec``; enqueued on ``stream``, no host synchronise."""
+        torch = self.torch
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        n = int(off.size)
+        for r, what in ((tp_rec, "tp_rec must be the float64 record tensor of Engine.true_peak on x's device"),
+                        (loud_rec, "loud_rec must be the float64 record tensor of Engine.loudness on x's device")):
+            if r is not None and (r.dtype != torch.float64 or not r.is_contiguous() or r.device != x.device or
+                                  r.numel() < 5 * n):
+                raise ValueError(what)
+        if tp_rec is None:
+            raise ValueError("tp_rec must be the float64 record tensor of Engine.true_peak on x's device")
+        if (loud_rec is None) != (target_lufs is None):
+            raise ValueError("loud_rec and target_lufs go together")
+        ceil = []
+        for c in (ceiling_tp, ceiling_peak):
+            v = 0.0 if c is None else float(c)
+            if c is not None and not v > 0.0:
+                raise ValueError("a ceiling must be positive")
+            ceil.append(v)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        with self._lock:
+            L.check(L.lib().msg_truepeak_gain(self._ctx, C.c_void_p(x.data_ptr()), channels,
+                                              off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              cnt.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                              None if loud_rec is None else C.c_void_p(loud_rec.data_ptr()),
+                                              C.c_void_p(tp_rec.data_ptr()),
+                                              0.0 if target_lufs is None else float(target_lufs), ceil[0], ceil[1],
+                                              C.c_void_p(stream.cuda_stream)), self._ctx)
+        return tp_rec
+
     # ---- last-batch inspection -----------------------------------------
     def last_plan(self):
         arr = (L.MsgPlanInfo * self._last_n)()

@@ -15,6 +15,7 @@
  *   msg_digest       per-render checksums on the device         (MS:1585-1589)
  *   msg_resample     sample-rate conversion of renders in HBM     (no counterpart: SURVEY §0)
  *   msg_loudness     BS.1770 integrated loudness and LUFS gain in HBM (no counterpart)
+ *   msg_truepeak     BS.1770 true peak and a dBTP ceiling in HBM   (no counterpart)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
 #ifndef MSGPU_H
@@ -116,7 +117,7 @@ int         msg_abi_version(void);
  * MSGPU_HOST_THREADS, else the CPU affinity / LOCAL_WORLD_SIZE, at most 16. */
 int         msg_host_threads(void);
 /* sizeof of the ABI structs (0 msg_preset, 1 msg_event, 2 msg_plan_info, 3 msg_digest_rec,
- * 4 msg_loudness_rec) for binding checks */
+ * 4 msg_loudness_rec, 5 msg_truepeak_rec) for binding checks */
 int64_t     msg_sizeof(int32_t which);
 msg_ctx*    msg_create(int device_ordinal);
 void        msg_destroy(msg_ctx* ctx);
@@ -297,6 +298,41 @@ int msg_loudness_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_
 /* The same definition as a sequential float64 loop over one signal in host memory
  * (x: n frames of `channels` interleaved words); needs no device. */
 int msg_loudness_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_loudness_rec* rec);
+
+/* ITU-R BS.1770-4 Annex 2 true peak of signals lying in HBM (csrc/truepeak.h holds the
+ * definition, DESIGN.md "True peak" the kernels): the signal oversampled by 4 below
+ * 96 kHz, by 2 below 192 kHz and not at all from there on, through a 24-tap-per-phase
+ * Kaiser-windowed Nyquist filter in float32 with a fixed order of fused steps; every
+ * maximum is taken over the bit patterns of |v|, so a NaN in the signal gives NaN.
+ *   true_peak  max(peak, max |oversampled value|), linear
+ *   peak       sample peak max |x| over every frame and channel
+ *   dbtp       20 log10(true_peak), correctly rounded; -inf for 0
+ *   gain       0 until msg_truepeak_gain writes the gain it applied
+ *   os         the oversampling factor used
+ * Host and device records agree to the bit; a signal's record does not depend on the
+ * batch it is measured in.  sr < 1: MSG_E_VALUE. */
+typedef struct msg_truepeak_rec {
+    double true_peak, peak, dbtp, gain;
+    int32_t os, pad;
+} msg_truepeak_rec;
+/* Signals as for msg_loudness; rec_dev: n_signals device records.  Enqueued on stream;
+ * one call in flight per context. */
+int msg_truepeak(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                 int32_t n_signals, int32_t sr, msg_truepeak_rec* rec_dev, void* stream);
+/* Scale each signal in place by (float)g, g formed on the device in float64 from its records:
+ *   g = 10^((target_lufs - lufs) / 20), msg_loudness_gain's expression; loud_rec_dev
+ *       NULL or lufs = -inf: g = 1;
+ *   ceiling_tp > 0 and g true_peak > ceiling_tp:  g = ceiling_tp / true_peak;
+ *   ceiling_peak > 0 and g peak > ceiling_peak:   g = ceiling_peak / peak.
+ * Both ceilings are linear.  Writes g to the true-peak record's gain and, when given,
+ * to the loudness record's.  With no ceiling binding the samples are msg_loudness_gain's
+ * to the bit.  The signals must not overlap.  Enqueued on stream. */
+int msg_truepeak_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                      int32_t n_signals, msg_loudness_rec* loud_rec_dev, msg_truepeak_rec* tp_rec_dev,
+                      double target_lufs, double ceiling_tp, double ceiling_peak, void* stream);
+/* The same definition as one loop over one signal in host memory (x: n frames of
+ * `channels` interleaved words); needs no device. */
+int msg_truepeak_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_truepeak_rec* rec);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
