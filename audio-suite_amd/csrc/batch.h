@@ -7,6 +7,7 @@
 #include <map>
 #include <vector>
 #include "rt.h"
+#include "gen_share.h"
 #include "launch.h"
 #include "../../include/msgpu.h"
 
@@ -130,6 +131,12 @@ struct Batch {
         std::vector<int32_t> ct_list;           // ct concatenated
         int32_t ct_off[SPEC_CT_PLANS + 1] = {0};
         int small_lds = 0, big_lds = 0;
+        // generator sharing (gen_share.h): float32-chain events, the owners among them
+        // (gen_list holds the owners only), the floats of the micro_last slots behind the
+        // micro pool, and per preset the offset msg_last_meta reads micro_last from
+        int64_t n_events = 0, n_owners = 0;
+        int64_t mlast_sum = 0;
+        std::vector<int64_t> micro_last;
     } f32;
 
     struct Fir64 {                              // float64 FIR of saturated renders (kernels_fir64.h)

@@ -115,6 +115,9 @@ struct Switches {
     int h_early = 2;
     bool er_dev = true;          // ER gains drawn on the device (k_er_gains; MSGPU_ER_DEV=0: on the host plan)
     int so_row = 0, so_col = 0;  // odd-stereo transform-split limits (MSGPU_SO_ROW / _COL, tests; 0 = default)
+    // each distinct generator grain once per batch (gen_share.h); MSGPU_GEN_SHARE=0: every
+    // event generates its own (the bit-identity tests and the A/B)
+    bool gen_share = true;
 
     static Switches from_env() {
         Switches w;
@@ -133,6 +136,7 @@ struct Switches {
         if (const char* e = getenv("MSGPU_ER_DEV")) w.er_dev = e[0] != '0';
         if (const char* e = getenv("MSGPU_SO_ROW")) w.so_row = atoi(e);
         if (const char* e = getenv("MSGPU_SO_COL")) w.so_col = atoi(e);
+        if (const char* e = getenv("MSGPU_GEN_SHARE")) w.gen_share = e[0] != '0';
         return w;
     }
 };
@@ -171,6 +175,9 @@ struct Prof {
     // plan sizes, plan events + tap merge, preset records, event records, lists + buffers
     double host_sum[8] = {0};
     double ola_fir_sum = 0.0;    // presets whose overlap-add ran inside k_fir8p, summed over profiled batches
+    // float32-chain events and the grains k_gen_normal generated for them (gen_share.h),
+    // summed over profiled batches
+    double gen_events_sum = 0.0, gen_grains_sum = 0.0;
     int64_t host_cnt = 0;
 
     hipError_t create_events() {
@@ -212,6 +219,7 @@ struct Prof {
         for (double& v : stage_sum) v = 0.0;
         for (double& v : host_sum) v = 0.0;
         ola_fir_sum = 0.0;
+        gen_events_sum = gen_grains_sum = 0.0;
         stage_cnt = 0;
         host_cnt = 0;
     }
@@ -344,6 +352,10 @@ struct msg_ctx {
     std::vector<int32_t> h_slot_base;
     std::vector<Ev64> h_ev64;
     std::vector<int32_t> h_last64;      // per preset: Ev64 index of its last event, -1 = float32 chain
+    std::vector<int64_t> h_micro_last;  // per float32-chain preset: its last event's micro_last in the micro pool
+    // generator sharing (gen_share.h): each event slot's owner and the lookup's buffers, kept between batches
+    std::vector<int32_t> h_gen_owner;
+    genshare::Scratch gen_scratch;
     int32_t last_n = 0;
 
     // What must come first and in this order; the members' destructors follow.

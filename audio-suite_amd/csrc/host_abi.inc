@@ -24,6 +24,27 @@ int msg_plan_host(const msg_preset* preset, const double* bp_bank, const double*
     return MSG_OK;
 }
 
+// The generator's owner assignment (gen_share.h) over every preset of a batch in
+// order: owner[slot] for the events at events[slot_base[p] + k], k < n_events[p].
+// For the tests of the host function; not part of the ABI.
+int msg_debug_gen_owners(const msg_preset* presets, int32_t n_presets, const msg_event* events,
+                         const int32_t* slot_base, const int32_t* n_events, int64_t n_slots, int32_t share,
+                         int32_t* owner, int64_t* n_owners) {
+    if (!presets || !events || !slot_base || !n_events || !owner || n_presets < 0)
+        return fail(nullptr, MSG_E_ARG, "bad arguments");
+    std::vector<int32_t> list((size_t)n_presets);
+    for (int32_t p = 0; p < n_presets; ++p) {
+        list[p] = p;
+        if (n_events[p] < 0 || slot_base[p] < 0 || (int64_t)slot_base[p] + n_events[p] > n_slots)
+            return fail(nullptr, MSG_E_ARG, "events outside the slots");
+    }
+    genshare::Scratch scratch;
+    const int64_t n = genshare::assign(presets, list.data(), n_presets, events, slot_base, n_events, n_slots,
+                                       share != 0, owner, scratch);
+    if (n_owners) *n_owners = n;
+    return MSG_OK;
+}
+
 // BS.1770-4 integrated loudness of one signal in host memory: the definition of
 // loudness.h as one sequential float64 loop (ld_host)
 int msg_loudness_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_loudness_rec* rec) {

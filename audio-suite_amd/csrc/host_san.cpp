@@ -18,6 +18,7 @@
 #include "ziggurat_tables.h"
 #include "nprng.h"
 #include "plan.h"
+#include "gen_share.h"
 #include "host_pool.h"
 #include "digest.h"
 #include "loudness.h"

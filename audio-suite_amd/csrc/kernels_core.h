@@ -212,6 +212,9 @@ MSG_DEV float gen_fade(const GenBasicConst& c, int j, float x) {
 }
 
 // RAW64: raw float64 normals for the float64 chain; else the float32 grain.
+// The float32 list holds only the owners of the batch's generator keys
+// (gen_share.h): whatever this kernel's output depends on besides the output
+// slot must be part of that key.
 // The float32 path forms the fast-path normal in float32 from the top 32 bits
 // of its 52-bit ziggurat integer (|error| <= 1 ulp of float32); slow draws and
 // RAW64 use the exact float64 product.

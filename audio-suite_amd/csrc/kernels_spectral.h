@@ -185,7 +185,7 @@ template <class L> MSG_DEV void drop_edge_imag(float2* buf, bool even, int n) {
 // loop (LICM) they stay live across the FFT engine's register peak and spill.
 template <class L, int T, class XF>
 MSG_DEV void spectral_chain(float2* lds, bool evn, const EventRt* __restrict__ ert, int ei, int n,
-                            float* micro, XF&& xf) {
+                            float* micro_pool, XF&& xf) {
     SPEC_STAMP_INIT;
     const int ops = ert[ei].ops;
     const bool tilt = (ops & (SPEC_TILT_NOISE | SPEC_TILT_SKEW)) != 0;
@@ -243,8 +243,14 @@ MSG_DEV void spectral_chain(float2* lds, bool evn, const EventRt* __restrict__ e
                                rxl_get<L>(lds, evn, j) * (float)exp((double)j * k_env) * fade_w(j, nn, fade));
                 __syncthreads();
             }
-            float* mo = opaque_ptr(micro);
-            for (int j = tid; j < nn; j += T) mo[j] = rxl_get<L>(lds, evn, j);
+            // kept for the preset's last event only (msg_last_meta), in the preset's slot
+            // behind the pool: the event's generator slot may be shared (gen_share.h)
+            // and is read-only
+            const int64_t mlast = ex.mlast_off;
+            if (mlast >= 0) {
+                float* mo = opaque_ptr(micro_pool) + mlast;
+                for (int j = tid; j < nn; j += T) mo[j] = rxl_get<L>(lds, evn, j);
+            }
         } else if (step == 2) {
             const int ops2 = ex.ops;
             int kz = KK;          // bins >= kz are zero, zeroing deferred to the next gather
@@ -301,21 +307,21 @@ k_spectral(const msg_preset* __restrict__ presets, const msg_event* __restrict__
     const msg_event& e = events[ei];
     const PresetRt& r = rt[e.preset];
     const int n = e.n;
-    float* micro = micro_pool + r.pool_base + e.pool_off;
+    const int64_t micro_off = ert[ei].micro_off;   // the owner's slot (gen_share.h), read-only
     float* grain = grain_pool + r.pool_base + e.pool_off;
     if (ert[ei].ops == 0) {   // no spectral stage: grain = micro
+        const float* micro = micro_pool + micro_off;
         for (int j = threadIdx.x; j < n; j += T) grain[j] = micro[j];
         return;
     }
     const RealPlan& rp = plans[ert[ei].plan];
     const bool evn = rp.even != 0;
-    // the whole grain in flight at once (float4 loads from the 16-byte aligned preset pool)
-    load_real_segment<LaySwz, T, (2 * MAXM + 4 * T - 1) / (4 * T)>(lds, evn, micro_pool + r.pool_base,
-                                                                   e.pool_off, n, threadIdx.x);
+    // the whole grain in flight at once (float4 loads from the 16-byte aligned pool)
+    load_real_segment<LaySwz, T, (2 * MAXM + 4 * T - 1) / (4 * T)>(lds, evn, micro_pool, micro_off, n, threadIdx.x);
     SPEC_STAMP(0);
     const TwLds tw = stage_twiddles<T>(lds + rp.lds_c, rp);   // includes the barrier
     SPEC_STAMP(1);
-    spectral_chain<LaySwz, T>(lds, evn, ert, ei, n, micro,
+    spectral_chain<LaySwz, T>(lds, evn, ert, ei, n, micro_pool,
                               [&](bool inv) { rtransform<T, MAXM, RSET_ALL>(lds, rp, tw, inv); });
     SPEC_STAMP_RESET;
     for (int j = threadIdx.x; j < n; j += T) grain[j] = rxl_get<LaySwz>(lds, evn, j);

@@ -551,7 +551,8 @@ int msg_gate(msg_ctx* ctx, msg_ctx* peer, int32_t wait_stage, int32_t record_sta
     return MSG_OK;
 }
 
-// ms[0..9] stage times, [10..17] host clocks, [18] fused overlap-adds per batch
+// ms[0..9] stage times, [10..17] host clocks, [18] fused overlap-adds per batch,
+// [19] float32-chain events per batch, [20] the grains the generator wrote for them
 int msg_stage_times(msg_ctx* ctx, float* ms, int32_t n) {
     if (!ctx || !ms) return MSG_E_ARG;
     Prof& pr = ctx->prof;
@@ -561,6 +562,8 @@ int msg_stage_times(msg_ctx* ctx, float* ms, int32_t n) {
     for (int i = 10; i < n && i < 18; ++i)
         ms[i] = pr.host_cnt ? (float)(pr.host_sum[i - 10] / (double)pr.host_cnt) : 0.f;
     if (n > 18) ms[18] = pr.host_cnt ? (float)(pr.ola_fir_sum / (double)pr.host_cnt) : 0.f;
+    if (n > 19) ms[19] = pr.host_cnt ? (float)(pr.gen_events_sum / (double)pr.host_cnt) : 0.f;
+    if (n > 20) ms[20] = pr.host_cnt ? (float)(pr.gen_grains_sum / (double)pr.host_cnt) : 0.f;
     return MSG_OK;
 }
 
@@ -1010,7 +1013,9 @@ int msg_last_meta(msg_ctx* ctx, int32_t preset, double* micro, double* grain, in
         return MSG_OK;
     }
     if (micro) {
-        HIPCHK(ctx, hipMemcpy(tmp.data(), ctx->micro.p + off, e.n * sizeof(float), hipMemcpyDeviceToHost));
+        // the generator's grain lies in its owner's slot, a tilted one in the preset's slot behind the pool
+        const int64_t moff = ctx->h_micro_last[preset] >= 0 ? ctx->h_micro_last[preset] : off;
+        HIPCHK(ctx, hipMemcpy(tmp.data(), ctx->micro.p + moff, e.n * sizeof(float), hipMemcpyDeviceToHost));
         for (int i = 0; i < e.n; ++i) micro[i] = tmp[i];
     }
     if (grain) {

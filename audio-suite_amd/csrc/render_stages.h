@@ -565,6 +565,37 @@ static int stage_event_records(msg_ctx* ctx, Batch& b) {
     Batch::F32& F = b.f32;
     std::vector<F32Lists>& f32l = F.per_preset;
     f32l.resize(F.presets.size());
+    // Generator sharing (gen_share.h): the first event of the batch with a generator
+    // key is its owner, and the only one on k_gen_normal's list; every event reads
+    // its owner's micro slot.  One pass on this thread, before the records: the
+    // first event in list order owns.  The tilt step's micro_last (the one write
+    // into a micro slot after the generator) goes to a slot of the preset's own
+    // behind the pool, for the preset's last event only, so a shared slot is never
+    // written.
+    if ((size_t)b.nslots > ctx->h_gen_owner.size()) ctx->h_gen_owner.resize((size_t)b.nslots + b.nslots / 4);
+    int32_t* const owner = ctx->h_gen_owner.data();
+    F.micro_last.assign(b.P, -1);
+    {
+        std::vector<int32_t> nev(b.P);
+        for (int p = 0; p < b.P; ++p) nev[p] = b.info[p].n_events;
+        F.n_owners = genshare::assign(b.presets, F.presets.data(), (int)F.presets.size(), ctx->h_events.data(),
+                                      b.slot_base.data(), nev.data(), b.nslots, ctx->sw.gen_share, owner,
+                                      ctx->gen_scratch);
+        for (int p : F.presets) {
+            const int ne = nev[p];
+            F.n_events += ne;
+            if (ne <= 0) continue;
+            const int last = b.slot_base[p] + ne - 1;
+            const int gm = b.presets[p].gen_mode;
+            if (gm == MSG_GEN_NOISE_BURST || gm == MSG_GEN_FALLBACK || gm == MSG_GEN_SKEWED) {   // spec_ops' tilt modes
+                F.micro_last[p] = b.pool + F.mlast_sum;
+                F.mlast_sum += (ctx->h_events[last].n + 3) & ~int64_t(3);
+            } else {
+                const msg_event& oe = ctx->h_events[owner[last]];
+                F.micro_last[p] = b.prt[oe.preset].pool_base + oe.pool_off;
+            }
+        }
+    }
     HostPool::get().run((int)F.presets.size(), [&](int i) {
         const int p = F.presets[i];
         const msg_preset& pr = b.presets[p];
@@ -589,10 +620,15 @@ static int stage_event_records(msg_ctx* ctx, Batch& b) {
             x.tilt_alpha = tilt_alpha;
             x.env_tau = env_tau;
             x.warp_power = pr.nl_warp_power;
-            L.gen.push_back(ei);
+            const msg_event& oe = ctx->h_events[owner[ei]];
+            x.micro_off = b.prt[oe.preset].pool_base + oe.pool_off;
+            x.mlast_off = (k == ne - 1 && (x.ops & (SPEC_TILT_NOISE | SPEC_TILT_SKEW))) ? F.micro_last[p] : -1;
+            if (owner[ei] == ei) L.gen.push_back(ei);
             const int ctp = (x.ops && b.use_ct) ? spectral_ct_plan(e.n) : -1;
+            // k_spec3 reads the micro slot and writes the grain slot in 8-byte pairs: both offsets even
             if (b.use_s3 && x.ops &&
-                spec3_eligible(e.n, x.ops, x.gen_sr, x.cutoff_gen, x.roll, x.stretch, r.pool_base + e.pool_off,
+                spec3_eligible(e.n, x.ops, x.gen_sr, x.cutoff_gen, x.roll, x.stretch,
+                               (r.pool_base + e.pool_off) | x.micro_off,
                                &x.s3_kb, &x.s3_kz, &x.s3_ky, &x.s3_inv_f, &x.s3_pad))
                 L.s3.push_back(ei);
             else if (ctp >= 0)
@@ -736,7 +772,7 @@ static int stage_buffers(msg_ctx* ctx, Batch& b) {
     HIPCHK(ctx, ctx->state64.ensure(G.state_sum));
     HIPCHK(ctx, ctx->so_r2.ensure(b.r2_sum));
     HIPCHK(ctx, ctx->so_A.ensure(b.so_M));
-    HIPCHK(ctx, ctx->micro.ensure(b.pool));
+    HIPCHK(ctx, ctx->micro.ensure(b.pool + b.f32.mlast_sum));   // the pool, then the presets' micro_last slots
     HIPCHK(ctx, ctx->grain.ensure(b.pool));
     HIPCHK(ctx, ctx->mono_a.ensure(b.ysum));
     HIPCHK(ctx, ctx->mono_y.ensure(b.ysum));
@@ -1091,6 +1127,8 @@ static void host_clocks(msg_ctx* ctx, const Batch& b) {
     ctx->prof.host_sum[6] += ms(b.hB, b.hC);
     ctx->prof.host_sum[7] += ms(b.hC, b.h2);
     ctx->prof.ola_fir_sum += b.fir.n_ola;
+    ctx->prof.gen_events_sum += (double)b.f32.n_events;
+    ctx->prof.gen_grains_sum += (double)b.f32.n_owners;
     ++ctx->prof.host_cnt;
 }
 
@@ -1101,5 +1139,6 @@ static void keep_mirrors(msg_ctx* ctx, const Batch& b) {
     ctx->h_slot_base = b.slot_base;
     ctx->h_ev64 = b.g64.ev;
     ctx->h_last64 = b.g64.last;
+    ctx->h_micro_last = b.f32.micro_last;
     ctx->last_n = b.P;
 }

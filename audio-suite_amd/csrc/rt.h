@@ -79,6 +79,13 @@ struct EventRt {
     // band of the band-pruned spectral kernel (spec3.h, host-computed by s3_band)
     int32_t s3_kb, s3_kz, s3_ky, s3_pad;   // s3_pad: k / f exact in float32 (wide band's gather)
     double s3_inv_f;
+    // the generator's grain the event reads: the absolute float offset of its owner's
+    // micro slot (gen_share.h), its own pool_base + pool_off when it is the owner.
+    // A shared slot is read-only after the generator
+    int64_t micro_off;
+    // where the tilt step writes micro_last (kernels_spectral.h): the preset's slot
+    // behind the micro pool for the preset's last event, -1 for every other event
+    int64_t mlast_off;
 };
 enum : int32_t {
     SPEC_TILT_NOISE = 1, SPEC_TILT_SKEW = 2, SPEC_LOWPASS = 4, SPEC_STRETCH = 8, SPEC_WARP = 16,

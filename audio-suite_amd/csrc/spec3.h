@@ -431,10 +431,10 @@ template <class P> MSG_DEV void s3_first(float2* buf, float2 (&v)[P::R1]) {
     }
 }
 template <class P>
-MSG_DEV void s3_load(const msg_event* __restrict__ events, const PresetRt* __restrict__ rt, const int32_t* __restrict__ ev_list,
+MSG_DEV void s3_load(const EventRt* __restrict__ ert, const int32_t* __restrict__ ev_list,
                      int li, const float* __restrict__ micro_pool, float2 (&v)[P::R1]) {
-    const msg_event& e = events[ev_list[li]];
-    const float2* z = reinterpret_cast<const float2*>(micro_pool + rt[e.preset].pool_base + e.pool_off);
+    // the owner's micro slot (gen_share.h): even, as the event's own (spec3_eligible)
+    const float2* z = reinterpret_cast<const float2*>(micro_pool + ert[ev_list[li]].micro_off);
     const int j = otid();
     if (j < P::NB1) {
 #pragma unroll
@@ -462,7 +462,7 @@ MSG_DEV void s3_chain(float2* buf, const float2* tab, const msg_event* __restric
     if constexpr (KE > 1) {
         const int l2 = li + (int)gridDim.x;
         float2 pre[P::R1];
-        if (l2 < n_list) s3_load<P>(events, rt, ev_list, l2, micro_pool, pre);   // in flight through event li
+        if (l2 < n_list) s3_load<P>(ert, ev_list, l2, micro_pool, pre);   // in flight through event li
         s3_rest<P>(buf, tab, ert, ev_list[li], off, grain_pool);
         if (l2 >= n_list) return;
         __syncthreads();                            // exchange B read before the next pass 1 writes
@@ -486,7 +486,7 @@ k_spec3(const msg_event* __restrict__ events, const EventRt* __restrict__ ert, c
     // table loads, then the grain's, all in flight; the table stores wait for the tables only
     TabCopy<P::TAB_USED, T> tc;
     tc.fetch(tables);
-    s3_load<P>(events, rt, ev_list, li, micro_pool, v);
+    s3_load<P>(ert, ev_list, li, micro_pool, v);
     tc.put(tab);
     s3_chain<P, S3_EVENTS>(buf, tab, events, ert, rt, ev_list, n_list, micro_pool, grain_pool, li, v);
 }

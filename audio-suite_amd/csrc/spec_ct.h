@@ -147,13 +147,12 @@ k_spectral_ct(const msg_event* __restrict__ events, const EventRt* __restrict__ 
     const msg_event& e = events[ei];
     const PresetRt& r = rt[e.preset];
     const int n = 2 * P::M;
-    float* micro = micro_pool + r.pool_base + e.pool_off;
     float* grain = grain_pool + r.pool_base + e.pool_off;
     { TabCopy<P::TAB_USED, T> tc; tc.fetch(tables); tc.put(tab); }   // one memory latency, not one per T entries
-    load_real_segment<LayId, T, P::Q4>(buf, true, micro_pool + r.pool_base, e.pool_off, n, threadIdx.x);
+    load_real_segment<LayId, T, P::Q4>(buf, true, micro_pool, ert[ei].micro_off, n, threadIdx.x);   // the owner's slot
     __syncthreads();
     SPEC_STAMP(0);
-    spectral_chain<LayId, T>(buf, true, ert, ei, n, micro, [&](bool inv) { ct_rtransform<P>(buf, tab, inv); });
+    spectral_chain<LayId, T>(buf, true, ert, ei, n, micro_pool, [&](bool inv) { ct_rtransform<P>(buf, tab, inv); });
     SPEC_STAMP_RESET;
     // grain out: packed pairs, 8-byte stores when the grain is 8-byte aligned
     if ((((uintptr_t)grain) & 7) == 0) {

@@ -65,8 +65,11 @@ class Engine:
         self._gate_peer = peer      # the peer context stays alive while this one gates on it
 
     def stage_times(self):
-        arr = (C.c_float * 19)()
-        L.check(L.lib().msg_stage_times(self._ctx, arr, 19), self._ctx)
+        """Per profiled batch: [0..9] stage times and [10..17] host clocks in ms, [18] presets
+        whose overlap-add ran inside the FIR kernel, [19] float32-chain events, [20] the grains
+        the generator wrote for them (fewer when events share a generator stream)."""
+        arr = (C.c_float * 21)()
+        L.check(L.lib().msg_stage_times(self._ctx, arr, 21), self._ctx)
         return list(arr)
 
     def alloc_output(self, packed: PackedBatch):
