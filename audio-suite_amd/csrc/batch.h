@@ -126,6 +126,8 @@ struct Batch {
         // upload (host_event_records 0.15 -> 0.22 ms per C3 sub-batch)
         struct Lists { std::vector<int32_t> gen, s3, ct[SPEC_CT_PLANS], small, pending; };
         std::vector<Lists> per_preset;
+        // the lists hold owners only: gen_list the generator owners, the others the events
+        // that run a spectral kernel (gen_share.h)
         std::vector<int32_t> gen_list, spec_small, spec_big, spec3;
         std::vector<int32_t> ct[SPEC_CT_PLANS]; // events of the compile-time spectral plans
         std::vector<int32_t> ct_list;           // ct concatenated
@@ -135,6 +137,7 @@ struct Batch {
         // (gen_list holds the owners only), the floats of the micro_last slots behind the
         // micro pool, and per preset the offset msg_last_meta reads micro_last from
         int64_t n_events = 0, n_owners = 0;
+        int64_t n_spec_runs = 0;                // events on a spectral list (specshare)
         int64_t mlast_sum = 0;
         std::vector<int64_t> micro_last;
     } f32;

@@ -118,6 +118,9 @@ struct Switches {
     // each distinct generator grain once per batch (gen_share.h); MSGPU_GEN_SHARE=0: every
     // event generates its own (the bit-identity tests and the A/B)
     bool gen_share = true;
+    // the float32 spectral chain once per distinct spectral key (gen_share.h, specshare);
+    // MSGPU_SPEC_SHARE=0: every event runs it.  MSGPU_GEN_SHARE=0 implies it: no micro grain is shared
+    bool spec_share = true;
 
     static Switches from_env() {
         Switches w;
@@ -137,7 +140,8 @@ struct Switches {
         if (const char* e = getenv("MSGPU_SO_ROW")) w.so_row = atoi(e);
         if (const char* e = getenv("MSGPU_SO_COL")) w.so_col = atoi(e);
         if (const char* e = getenv("MSGPU_GEN_SHARE")) w.gen_share = e[0] != '0';
-        return w;
+        if (const char* e = getenv("MSGPU_SPEC_SHARE")) w.spec_share = e[0] != '0';
+        if (!w.gen_share) w.spec_share = false;        return w;
     }
 };
 
@@ -178,6 +182,7 @@ struct Prof {
     // float32-chain events and the grains k_gen_normal generated for them (gen_share.h),
     // summed over profiled batches
     double gen_events_sum = 0.0, gen_grains_sum = 0.0;
+    double spec_runs_sum = 0.0;  // float32-chain events that ran a spectral kernel (specshare)
     int64_t host_cnt = 0;
 
     hipError_t create_events() {
@@ -219,7 +224,7 @@ struct Prof {
         for (double& v : stage_sum) v = 0.0;
         for (double& v : host_sum) v = 0.0;
         ola_fir_sum = 0.0;
-        gen_events_sum = gen_grains_sum = 0.0;
+        gen_events_sum = gen_grains_sum = spec_runs_sum = 0.0;
         stage_cnt = 0;
         host_cnt = 0;
     }
@@ -275,6 +280,7 @@ struct msg_ctx {
     DevBuf<double> er_gain_d;           // k_er_gains' output (host batch path)
     DevBuf<double> er_tap_d;            // k_er_gains' per-tap gains
     Slice<EventRt> ert;
+    Slice<int64_t> grain_off;           // per event slot: the grain the overlap-add reads (specshare)
     Slice<PresetRt> prt;
     Slice<int32_t> gen_list, spec_small, spec_big, tile_begin, fir_begin, h_begin, st_begin, fir_plan_of;
     DevBuf<float> micro, grain, mono_a, mono_y;
@@ -356,6 +362,13 @@ struct msg_ctx {
     // generator sharing (gen_share.h): each event slot's owner and the lookup's buffers, kept between batches
     std::vector<int32_t> h_gen_owner;
     genshare::Scratch gen_scratch;
+    // spectral sharing (gen_share.h, specshare): each float32-chain slot's spectral owner and
+    // kernel route, and per event slot the absolute float offset of the grain its readers
+    // take (the owner's slot; a float64-chain event's own), uploaded as grain_off
+    std::vector<int32_t> h_spec_owner;
+    std::vector<int8_t> h_spec_route;
+    std::vector<int64_t> h_grain_off;
+    specshare::Scratch spec_scratch;
     int32_t last_n = 0;
 
     // What must come first and in this order; the members' destructors follow.

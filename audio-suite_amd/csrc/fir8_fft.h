@@ -245,12 +245,13 @@ struct OlaEv {
     float amp;
     int64_t goff;
 };
-MSG_DEV OlaEv ola_ev(const msg_event* __restrict__ ev, const PresetRt& pr, int k) {
+// goff: the preset's part of the per-slot grain offsets (the spectral owners' slots, gen_share.h)
+MSG_DEV OlaEv ola_ev(const msg_event* __restrict__ ev, const int64_t* __restrict__ goff, const PresetRt& pr, int k) {
     OlaEv o{INT32_MAX, 0, 0.f, 0};
     if (k < pr.n_events) {
         const msg_event& e = ev[k];
         o.s = e.start; o.L = e.len; o.amp = (float)e.amp;
-        o.goff = pr.pool_base + e.pool_off + e.offset;
+        o.goff = goff[k] + e.offset;
     }
     return o;
 }
@@ -260,7 +261,8 @@ MSG_DEV OlaEv ola_ev(const msg_event* __restrict__ ev, const PresetRt& pr, int k
 // lo + lane (fetched once per segment, for both halves).  (Two events per
 // iteration, both grains' loads in flight before the first FMA, ran slower:
 // 146 SGPR spills, C5's FIR 5.84 -> 6.10 ms per sub-batch.)
-MSG_DEV void ola_sum(const msg_event* __restrict__ ev, const PresetRt& pr, const float* __restrict__ grain_pool,
+MSG_DEV void ola_sum(const msg_event* __restrict__ ev, const int64_t* __restrict__ goff, const PresetRt& pr,
+                     const float* __restrict__ grain_pool,
                      int lo, const OlaEv& first, int64_t c0, float (&acc)[OLA_J]) {
     const int t = otid();
     const int lane = t & 63, w = t >> 6;
@@ -294,7 +296,7 @@ MSG_DEV void ola_sum(const msg_event* __restrict__ ev, const PresetRt& pr, const
         if (before != ~0ull) break;
         k0 += 64;
         if (k0 >= pr.n_events) break;
-        e = ola_ev(ev, pr, k0 + lane);
+        e = ola_ev(ev, goff, pr, k0 + lane);
     }
     const int64_t n = pr.out_n;
 #pragma unroll
@@ -309,22 +311,23 @@ MSG_DEV void ola_sum(const msg_event* __restrict__ ev, const PresetRt& pr, const
 // products as dif_split on the loaded halves)
 // lo: the first event that can reach s0 (its start after s0 - max_n; the host
 // computes it per block, fir_lo)
-MSG_DEV void ola_split(const msg_event* __restrict__ ev, const PresetRt& pr, const float* __restrict__ grain_pool,
+MSG_DEV void ola_split(const msg_event* __restrict__ ev, const int64_t* __restrict__ goff, const PresetRt& pr,
+                       const float* __restrict__ grain_pool,
                        int64_t s0, int lo, float2* buf, const float2* tab, float2 (&a)[R1], float2 (&b)[R1]) {
     const int t = otid();
     const int lane = t & 63, w = t >> 6;
-    const OlaEv first = ola_ev(ev, pr, lo + lane);
+    const OlaEv first = ola_ev(ev, goff, pr, lo + lane);
     float* xf = reinterpret_cast<float*>(buf) + w * OLA_CHUNK + lane;   // buf is free: inv_half ends on a barrier
     {
         float x0[OLA_J];
-        ola_sum(ev, pr, grain_pool, lo, first, s0, x0);
+        ola_sum(ev, goff, pr, grain_pool, lo, first, s0, x0);
 #pragma unroll
         for (int j = 0; j < OLA_J; ++j) xf[64 * j] = x0[j];             // read back by this lane only
     }
     float d[OLA_J];
     {
         float x1[OLA_J];
-        ola_sum(ev, pr, grain_pool, lo, first, s0 + M, x1);
+        ola_sum(ev, goff, pr, grain_pool, lo, first, s0 + M, x1);
 #pragma unroll
         for (int j = 0; j < OLA_J; ++j) {
             const float x0 = xf[64 * j];
@@ -451,7 +454,7 @@ template <bool OLA>
 __global__ void __launch_bounds__(fir8::T)
 k_fir8p(const PresetRt* __restrict__ rt, const int2* __restrict__ jobs, int n_jobs, const float2* __restrict__ tables,
         const float2* __restrict__ hspec, const float* __restrict__ x_in, float* __restrict__ y_out,
-        int32_t* __restrict__ ctr, const msg_event* __restrict__ events,
+        int32_t* __restrict__ ctr, const msg_event* __restrict__ events, const int64_t* __restrict__ grain_off,
         const float* __restrict__ grain_pool, const int32_t* __restrict__ ev_lo) {
     using namespace fir8;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
@@ -492,7 +495,8 @@ k_fir8p(const PresetRt* __restrict__ rt, const int2* __restrict__ jobs, int n_jo
         float2 a[R1], b[R1];
         const bool ola = OLA && __builtin_amdgcn_readfirstlane(pr.ola_fir);
         if (ola)
-            ola_split(events + pr.ev_begin, pr, grain_pool, t0 - (P - 1), ev_lo[lo + cur], buf, tab, a, b);
+            ola_split(events + pr.ev_begin, grain_off + pr.ev_begin, pr, grain_pool, t0 - (P - 1), ev_lo[lo + cur], buf,
+                      tab, a, b);
         else
             load_halves(x_in + pr.y_off, n, t0 - (P - 1), a, b);
         if (t == 0) s_take[par] = atomicAdd(ctr + xr * FIR8P_CTR, 1);   // the block after this one

@@ -1,4 +1,5 @@
-// gen_share.h — host: which events of a batch generate their grain.
+// gen_share.h — host: which events of a batch generate their grain, and which run
+// the float32 spectral chain on it (specshare, below).
 //
 // The reference draws event i of a render from default_rng(seed + i) (MS:650-686),
 // and a batch of variants (seeds x unfolds x stretches, msgpu/batch.py) repeats
@@ -22,6 +23,7 @@
 // msg_debug_gen_owners (host_abi.inc).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -146,3 +148,131 @@ inline int64_t assign(const msg_preset* presets, const int32_t* list, int L, con
 }
 
 }  // namespace genshare
+
+// ---------------------------------------------------------------------------
+// Spectral sharing: which float32-chain events of a batch run a spectral kernel.
+//
+// The float32 spectral chain of an event (k_spec3, k_spectral_ct, k_spectral and
+// its ops == 0 copy) reads the event's micro grain and, of its EventRt, ops, n,
+// gen_sr, cutoff_gen, roll, stretch, tilt_alpha, env_tau and warp_power; amp,
+// start, offset and len enter in the overlap-add only.  Two events with the
+// same generator owner, the same bits in those fields and the same kernel route
+// therefore get the same grain, bit for bit: the first event in list order with
+// such a key (its spectral owner) runs, and every reader of the grain pool takes
+// the owner's slot (the per-slot grain offsets).  An event that has a
+// micro_last to write (mlast_off >= 0) always runs: it may own a key, it never
+// borrows one.  A field the spectral kernels come to read belongs in same_key.
+//
+// The owners of a generator grain are chained off the generator owner's slot
+// (head, next), so an event costs one step per distinct parameter set of its
+// grain, and an event that is its own generator owner is never looked up.
+// ---------------------------------------------------------------------------
+enum : int32_t {
+    SPEC_TILT_NOISE = 1, SPEC_TILT_SKEW = 2, SPEC_LOWPASS = 4, SPEC_STRETCH = 8, SPEC_WARP = 16,
+};
+constexpr int32_t SPEC3_N = 37500;   // k_spec3's grain length (spec3.h)
+
+namespace specshare {
+
+// Stages of the float32 chain one event runs (EventRt::ops).
+inline int32_t spec_ops(const msg_preset& p, const msg_event& e) {
+    int32_t ops = 0;
+    if (p.gen_mode == MSG_GEN_NOISE_BURST || p.gen_mode == MSG_GEN_FALLBACK) ops |= SPEC_TILT_NOISE;
+    if (p.gen_mode == MSG_GEN_SKEWED) ops |= SPEC_TILT_SKEW;
+    if ((p.flags & MSG_F_BANDLIMIT) && e.n >= 8) ops |= SPEC_LOWPASS;
+    if ((p.flags & MSG_F_NL_WARP) && e.n >= 16) ops |= SPEC_WARP;
+    if (!(p.flags & MSG_F_PARTIAL_LOCK) && e.n >= 16 && std::fabs(e.stretch - 1.0) >= 1e-9) ops |= SPEC_STRETCH;
+    return ops;
+}
+
+// The preset's constants of the tilt step.
+struct PresetConsts { double tilt_alpha, env_tau; };
+inline PresetConsts preset_consts(const msg_preset& pr) {
+    const double tilt = pr.gen_mode == MSG_GEN_FALLBACK ? -3.0 : pr.noise_tilt;
+    return {std::log(std::pow(10.0, tilt / 20.0)) / std::log(2.0),
+            std::max(1e-6, (pr.micro_ms / 1000.0) * (pr.gen_mode == MSG_GEN_SKEWED ? 0.2 : 0.25))};
+}
+
+// The key's fields of one event, into an EventRt or the debug hook's record.
+template <class Rec>
+inline void key_fields(const msg_preset& pr, const msg_event& e, const PresetConsts& c, Rec& x) {
+    x.n = e.n;
+    x.gen_sr = e.gen_sr;
+    x.ops = spec_ops(pr, e);
+    x.cutoff_gen = e.cutoff_out * e.ufac;
+    x.roll = pr.bandlimit_roll_hz;
+    x.stretch = e.stretch;
+    x.tilt_alpha = c.tilt_alpha;
+    x.env_tau = c.env_tau;
+    x.warp_power = pr.nl_warp_power;
+}
+
+template <class Rec> inline bool same_key(const Rec& a, const Rec& b) {
+    using genshare::bits_of;
+    return a.ops == b.ops && a.n == b.n && a.gen_sr == b.gen_sr && bits_of(a.cutoff_gen) == bits_of(b.cutoff_gen) &&
+           bits_of(a.roll) == bits_of(b.roll) && bits_of(a.stretch) == bits_of(b.stretch) &&
+           bits_of(a.tilt_alpha) == bits_of(b.tilt_alpha) && bits_of(a.env_tau) == bits_of(b.env_tau) &&
+           bits_of(a.warp_power) == bits_of(b.warp_power);
+}
+
+// Kernel routes: the class of kernel an event alone would run (stage_event_records).
+enum : int8_t { ROUTE_COPY = 0, ROUTE_RUNTIME = 1, ROUTE_SPEC3 = 2, ROUTE_CT = 3 /* + plan */ };
+
+// Where the spectral kernels are not linked (the debug hook, the host-only build): the
+// route is a function of the key's fields and, for k_spec3's length, of the parity of the
+// event's grain offset and its micro offset (spec3_eligible), so the parity stands in.
+inline int8_t route_standin(int32_t ops, int32_t n, int64_t grain_off, int64_t micro_off) {
+    if (!ops) return ROUTE_COPY;
+    return (int8_t)(ROUTE_RUNTIME + (n == SPEC3_N ? ((grain_off | micro_off) & 1) : 0));
+}
+
+struct Scratch {
+    std::vector<int32_t> head;   // per generator-owner slot: the newest spectral owner of its grain
+    std::vector<int32_t> next;   // per spectral-owner slot: the next owner of the same grain, -1 = none
+};
+
+// owner[slot] for every event of the presets list[0, L), as genshare::assign: the slot
+// of the first event in list order with the same spectral key, the event's own slot when
+// it runs itself.  rec[slot]: the key's fields and mlast_off; route[slot]: the kernel
+// route; gen_owner: genshare::assign's result.  share == false: every event runs.
+// Returns the number of events that run.
+template <class Rec>
+inline int64_t assign(const Rec* rec, const int8_t* route, const int32_t* gen_owner, const int32_t* list, int L,
+                      const int32_t* slot_base, const int32_t* n_events, int64_t nslots, bool share,
+                      int32_t* owner, Scratch& S) {
+    int64_t runs = 0;
+    if (!share) {
+        for (int i = 0; i < L; ++i)
+            for (int32_t k = 0, s = slot_base[list[i]]; k < n_events[list[i]]; ++k) owner[s + k] = s + k;
+        for (int i = 0; i < L; ++i) runs += n_events[list[i]];
+        return runs;
+    }
+    if (S.head.size() < (size_t)nslots) { S.head.resize((size_t)nslots); S.next.resize((size_t)nslots); }
+    int32_t* const head = S.head.data();
+    int32_t* const next = S.next.data();
+    for (int i = 0; i < L; ++i) {
+        const int p = list[i];
+        for (int32_t k = 0, s = slot_base[p]; k < n_events[p]; ++k) {
+            const int32_t e = s + k, g = gen_owner[e];
+            owner[e] = e;
+            ++runs;
+            if (g == e) {                    // the grain's first event: a new chain, no lookup
+                head[e] = e;
+                next[e] = -1;
+                continue;
+            }
+            int32_t o = head[g];
+            while (o >= 0 && !(route[o] == route[e] && same_key(rec[o], rec[e]))) o = next[o];
+            if (o < 0) {                     // a new parameter set of the grain
+                next[e] = head[g];
+                head[g] = e;
+            } else if (rec[e].mlast_off < 0) {
+                owner[e] = o;
+                --runs;
+            }
+        }
+    }
+    return runs;
+}
+
+}  // namespace specshare

@@ -45,6 +45,52 @@ int msg_debug_gen_owners(const msg_preset* presets, int32_t n_presets, const msg
     return MSG_OK;
 }
 
+// The spectral owner assignment (gen_share.h, specshare) over the same arguments, every
+// preset taken as a float32-chain preset with the default kernel switches:
+// owner[slot] is the slot whose grain the event's readers take, the event's own when it
+// runs a spectral kernel itself; gen_owner[slot] (optional) the generator's owner.
+// The kernel route is taken from specshare::route_standin (the spectral kernels are not
+// part of the host-only build).  For the tests of the host function; not part of the ABI.
+int msg_debug_spec_owners(const msg_preset* presets, int32_t n_presets, const msg_event* events,
+                          const int32_t* slot_base, const int32_t* n_events, int64_t n_slots, int32_t gen_share,
+                          int32_t spec_share, int32_t* owner, int32_t* gen_owner, int64_t* n_runs) {
+    if (!presets || !events || !slot_base || !n_events || !owner || n_presets < 0)
+        return fail(nullptr, MSG_E_ARG, "bad arguments");
+    std::vector<int32_t> list((size_t)n_presets);
+    for (int32_t p = 0; p < n_presets; ++p) {
+        list[p] = p;
+        if (n_events[p] < 0 || slot_base[p] < 0 || (int64_t)slot_base[p] + n_events[p] > n_slots)
+            return fail(nullptr, MSG_E_ARG, "events outside the slots");
+    }
+    struct Rec {
+        int32_t ops, n, gen_sr;
+        double cutoff_gen, roll, stretch, tilt_alpha, env_tau, warp_power;
+        int64_t mlast_off;
+    };
+    std::vector<int32_t> gown((size_t)std::max<int64_t>(n_slots, 1));
+    std::vector<Rec> rec((size_t)std::max<int64_t>(n_slots, 1));
+    std::vector<int8_t> route((size_t)std::max<int64_t>(n_slots, 1));
+    genshare::Scratch gscratch;
+    genshare::assign(presets, list.data(), n_presets, events, slot_base, n_events, n_slots, gen_share != 0,
+                     gown.data(), gscratch);
+    for (int32_t p = 0; p < n_presets; ++p) {
+        const specshare::PresetConsts pc = specshare::preset_consts(presets[p]);
+        for (int32_t k = 0, s = slot_base[p]; k < n_events[p]; ++k) {
+            Rec& x = rec[s + k];
+            specshare::key_fields(presets[p], events[s + k], pc, x);
+            x.mlast_off = (k == n_events[p] - 1 && (x.ops & (SPEC_TILT_NOISE | SPEC_TILT_SKEW))) ? 0 : -1;
+            // preset regions start 16-byte aligned: pool_off carries the offsets' parity
+            route[s + k] = specshare::route_standin(x.ops, x.n, events[s + k].pool_off, events[gown[s + k]].pool_off);
+            if (gen_owner) gen_owner[s + k] = gown[s + k];
+        }
+    }
+    specshare::Scratch scratch;
+    const int64_t n = specshare::assign(rec.data(), route.data(), gown.data(), list.data(), n_presets, slot_base,
+                                        n_events, n_slots, gen_share != 0 && spec_share != 0, owner, scratch);
+    if (n_runs) *n_runs = n;
+    return MSG_OK;
+}
+
 // BS.1770-4 integrated loudness of one signal in host memory: the definition of
 // loudness.h as one sequential float64 loop (ld_host)
 int msg_loudness_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_loudness_rec* rec) {

@@ -19,6 +19,7 @@ bool spec3_tables(std::vector<float>& out) {
 bool spec3_eligible(int n, int ops, int gen_sr, double cutoff_gen, double roll, double stretch, int64_t float_off,
                     int32_t* kb, int32_t* kz, int32_t* ky, double* inv_f, int32_t* exact32) {
     using P = Spec3P18750;
+    static_assert(2 * P::M == SPEC3_N, "gen_share.h's route stand-in knows this length");
     if (n != 2 * P::M || (float_off & 1)) return false;
     if (ops & (SPEC_TILT_NOISE | SPEC_TILT_SKEW | SPEC_WARP)) return false;
     if (!(ops & SPEC_LOWPASS)) return false;

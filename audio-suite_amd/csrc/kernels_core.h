@@ -473,9 +473,11 @@ k_er_gains(const msg_preset* __restrict__ presets, const PresetRt* __restrict__ 
 MSG_DEV int job_order() { return xcd_block(blockIdx.x, gridDim.x); }
 
 // One OLA_TILE tile [t0, t0 + OLA_TILE) of preset r: the placed grains in event
-// order times the ADSR (MS:742-764), into its mono buffer.
-MSG_DEV void ola_tile(const msg_event* __restrict__ events, const PresetRt& r, int64_t t0,
-                      const float* __restrict__ grain_pool, float* __restrict__ mono) {
+// order times the ADSR (MS:742-764), into its mono buffer.  grain_off: per event
+// slot, the grain's absolute offset in the pool -- its spectral owner's slot
+// (gen_share.h), which holds the event's own n samples.
+MSG_DEV void ola_tile(const msg_event* __restrict__ events, const int64_t* __restrict__ grain_off, const PresetRt& r,
+                      int64_t t0, const float* __restrict__ grain_pool, float* __restrict__ mono) {
     const int64_t t1 = t0 + OLA_TILE < r.out_n ? t0 + OLA_TILE : r.out_n;
     constexpr int PER = OLA_TILE / OLA_T;
     const int lane = threadIdx.x & 63;
@@ -495,7 +497,7 @@ MSG_DEV void ola_tile(const msg_event* __restrict__ events, const PresetRt& r, i
         if (k < r.n_events) {
             const msg_event& e = ev[k];
             s = e.start; L = e.len; amp = (float)e.amp;
-            goff = r.pool_base + e.pool_off + e.offset;
+            goff = grain_off[r.ev_begin + k] + e.offset;
         }
         const uint64_t live = __ballot(s < t1);           // sorted: a prefix of the lanes
         const int cnt = __popcll(live);
@@ -540,27 +542,27 @@ MSG_DEV void ola_tile(const msg_event* __restrict__ events, const PresetRt& r, i
 }
 
 __global__ void __launch_bounds__(OLA_T)
-k_ola_env(const msg_event* __restrict__ events, const PresetRt* __restrict__ rt,
-          const int32_t* __restrict__ tile_begin, int n_presets,
+k_ola_env(const msg_event* __restrict__ events, const int64_t* __restrict__ grain_off,
+          const PresetRt* __restrict__ rt, const int32_t* __restrict__ tile_begin, int n_presets,
           const float* __restrict__ grain_pool, float* __restrict__ mono) {
     const int b = job_order();
     const int p = find_preset(tile_begin, n_presets, b);
     const PresetRt& r = rt[p];
-    ola_tile(events, r, (int64_t)(b - r.tile_begin) * OLA_TILE, grain_pool, mono);
+    ola_tile(events, grain_off, r, (int64_t)(b - r.tile_begin) * OLA_TILE, grain_pool, mono);
 }
 
 // The overlap-add of the float64 FIR's slots (kernels_fir64.h) among the presets
 // whose overlap-add runs inside k_fir8p (ola_fir): the float64 FIR reads their
 // mono a, which k_fir8p never writes.  A grid-stride walk over (slot, tile).
 __global__ void __launch_bounds__(OLA_T)
-k_ola_slots(const msg_event* __restrict__ events, const PresetRt* __restrict__ rt,
-            const int32_t* __restrict__ slot_preset, const int32_t* __restrict__ n_slots, int tmax,
+k_ola_slots(const msg_event* __restrict__ events, const int64_t* __restrict__ grain_off,
+            const PresetRt* __restrict__ rt, const int32_t* __restrict__ slot_preset, const int32_t* __restrict__ n_slots, int tmax,
             const float* __restrict__ grain_pool, float* __restrict__ mono) {
     const int ns = *n_slots;
     for (int64_t j = blockIdx.x; j < (int64_t)ns * tmax; j += gridDim.x) {   // 64-bit: ns * tmax can pass 2^31
         const int sl = (int)(j / tmax), t = (int)(j - (int64_t)sl * tmax);
         const PresetRt& r = rt[__builtin_amdgcn_readfirstlane(slot_preset[sl])];
         if (!r.ola_fir || (int64_t)t * OLA_TILE >= r.out_n) continue;   // uniform
-        ola_tile(events, r, (int64_t)t * OLA_TILE, grain_pool, mono);
+        ola_tile(events, grain_off, r, (int64_t)t * OLA_TILE, grain_pool, mono);
     }
 }

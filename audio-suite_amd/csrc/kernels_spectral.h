@@ -293,6 +293,10 @@ MSG_DEV void spectral_chain(float2* lds, bool evn, const EventRt* __restrict__ e
 }
 
 // Runtime-plan kernel: any grain length (Bluestein for non-7-smooth lengths).
+// The lists of the float32 spectral kernels (this one, k_spectral_ct, k_spec3) hold only
+// the owners of the batch's spectral keys (gen_share.h, specshare): whatever of EventRt,
+// msg_event or the preset these kernels come to read, besides the micro grain and the
+// output slot, must be part of that key (specshare::same_key).
 template <int T, int MAXM>
 __global__ void __launch_bounds__(T)
 k_spectral(const msg_preset* __restrict__ presets, const msg_event* __restrict__ events,

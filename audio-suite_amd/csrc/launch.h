@@ -98,9 +98,10 @@ hipError_t launch_fir8(unsigned grid, hipStream_t s, const PresetRt* rt, const i
                        const float2* hspec, const float* x_in, float* y_out);
 hipError_t launch_fir8p(unsigned n_jobs, unsigned grid, hipStream_t s, const PresetRt* rt, const int2* jobs,
                         const float2* tables, const float2* hspec, const float* x_in, float* y_out, int32_t* ctr,
-                        const msg_event* events, const float* grain_pool,
-                        const int32_t* ev_lo);   // events: null if no ola_fir preset; ev_lo: per job, the
-                                                 // first event reaching its segment
+                        const msg_event* events, const int64_t* grain_off, const float* grain_pool,
+                        const int32_t* ev_lo);   // events: null if no ola_fir preset; grain_off: per event
+                                                 // slot, its grain in the pool; ev_lo: per job, the first
+                                                 // event reaching its segment
 // two partitions of N / 2 taps on the N = 65536 engine (fir8_fft.h k_fir8q): B = P = 32768,
 // runs (signal, first block) of run_len blocks; the signal's PresetRt::fir_Q holds its block count
 constexpr int FIR8Q_P = FIR8_N / 2;

@@ -243,15 +243,7 @@ static void choose_fir(int64_t M, int64_t n, int& N, int& P, int& Q, bool fir8, 
     }
 }
 
-static int spec_ops(const msg_preset& p, const msg_event& e) {
-    int ops = 0;
-    if (p.gen_mode == MSG_GEN_NOISE_BURST || p.gen_mode == MSG_GEN_FALLBACK) ops |= SPEC_TILT_NOISE;
-    if (p.gen_mode == MSG_GEN_SKEWED) ops |= SPEC_TILT_SKEW;
-    if ((p.flags & MSG_F_BANDLIMIT) && e.n >= 8) ops |= SPEC_LOWPASS;
-    if ((p.flags & MSG_F_NL_WARP) && e.n >= 16) ops |= SPEC_WARP;
-    if (!(p.flags & MSG_F_PARTIAL_LOCK) && e.n >= 16 && std::fabs(e.stretch - 1.0) >= 1e-9) ops |= SPEC_STRETCH;
-    return ops;
-}
+using specshare::spec_ops;   // gen_share.h: shared with the host-only build
 
 // Presets whose grains run the float64 chain (kernels_grain64.h): the
 // generators outside the normal-driven closed forms, and every stage whose
@@ -552,7 +544,8 @@ int msg_gate(msg_ctx* ctx, msg_ctx* peer, int32_t wait_stage, int32_t record_sta
 }
 
 // ms[0..9] stage times, [10..17] host clocks, [18] fused overlap-adds per batch,
-// [19] float32-chain events per batch, [20] the grains the generator wrote for them
+// [19] float32-chain events per batch, [20] the grains the generator wrote for them,
+// [21] the events among them that ran a spectral kernel
 int msg_stage_times(msg_ctx* ctx, float* ms, int32_t n) {
     if (!ctx || !ms) return MSG_E_ARG;
     Prof& pr = ctx->prof;
@@ -564,6 +557,7 @@ int msg_stage_times(msg_ctx* ctx, float* ms, int32_t n) {
     if (n > 18) ms[18] = pr.host_cnt ? (float)(pr.ola_fir_sum / (double)pr.host_cnt) : 0.f;
     if (n > 19) ms[19] = pr.host_cnt ? (float)(pr.gen_events_sum / (double)pr.host_cnt) : 0.f;
     if (n > 20) ms[20] = pr.host_cnt ? (float)(pr.gen_grains_sum / (double)pr.host_cnt) : 0.f;
+    if (n > 21) ms[21] = pr.host_cnt ? (float)(pr.spec_runs_sum / (double)pr.host_cnt) : 0.f;
     return MSG_OK;
 }
 
@@ -712,7 +706,8 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
             const unsigned grid = (unsigned)std::max(MSG_XCDS, (std::min(nj, ctx->n_cu) / MSG_XCDS) * MSG_XCDS);
             HIPCHK(ctx, fir8_counters(ctx, s));
             HIPCHK(ctx, launch_fir8p((unsigned)nj, grid, s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab.p,
-                                     ctx->sf_hspec.p, x_dev, y_dev, ctx->fir8_ctr.p, nullptr, nullptr, nullptr));
+                                     ctx->sf_hspec.p, x_dev, y_dev, ctx->fir8_ctr.p, nullptr, nullptr, nullptr,
+                                     nullptr));
         } else {
             HIPCHK(ctx, launch_fir8((unsigned)fj.size(), s, ctx->sf_prt.p, ctx->sf_jobs.p, ctx->d_fir4tab.p,
                                     ctx->sf_hspec.p, x_dev, y_dev));
@@ -1019,7 +1014,9 @@ int msg_last_meta(msg_ctx* ctx, int32_t preset, double* micro, double* grain, in
         for (int i = 0; i < e.n; ++i) micro[i] = tmp[i];
     }
     if (grain) {
-        HIPCHK(ctx, hipMemcpy(tmp.data(), ctx->grain.p + off, e.n * sizeof(float), hipMemcpyDeviceToHost));
+        // the grain lies in its spectral owner's slot (gen_share.h)
+        const int64_t goff = ctx->h_grain_off[(size_t)ctx->h_slot_base[preset] + inf.n_events - 1];
+        HIPCHK(ctx, hipMemcpy(tmp.data(), ctx->grain.p + goff, e.n * sizeof(float), hipMemcpyDeviceToHost));
         for (int i = 0; i < e.n; ++i) grain[i] = tmp[i];
     }
     *n = e.n;

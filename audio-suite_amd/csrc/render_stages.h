@@ -466,6 +466,7 @@ static int rec_events64(msg_ctx* ctx, Batch& b, int p) {
         v.ei = ei;
         v.off64 = G.sum;
         v.grain_off = r.pool_base + e.pool_off;
+        ctx->h_grain_off[ei] = v.grain_off;          // float64-chain events keep their own slots
         v.cutoff_gen = e.cutoff_out * e.ufac;
         v.stretch = e.stretch;
         if (v.ops & G64_CEP) { v.save_off = G.save_sum; G.save_sum += e.n / 2 + 1; }
@@ -505,12 +506,16 @@ static int stage_preset_records(msg_ctx* ctx, Batch& b) {
         ctx->h_ert_cap = (size_t)b.nslots + b.nslots / 4;
     }
     b.ert = ctx->h_ert.get();
+    if ((size_t)b.nslots > ctx->h_grain_off.size()) ctx->h_grain_off.resize((size_t)b.nslots + b.nslots / 4);
     // slots a preset reserves beyond its events are never written: zero them
     // so the whole uploaded range is defined
     for (int p = 0; p < P; ++p)
-        if (b.info[p].n_slots > b.info[p].n_events)
+        if (b.info[p].n_slots > b.info[p].n_events) {
             memset(b.ert + b.slot_base[p] + b.info[p].n_events, 0,
                    sizeof(EventRt) * (size_t)(b.info[p].n_slots - b.info[p].n_events));
+            std::fill_n(ctx->h_grain_off.begin() + b.slot_base[p] + b.info[p].n_events,
+                        b.info[p].n_slots - b.info[p].n_events, int64_t(0));
+        }
     b.f64.rt.resize(P);
     b.st_count.resize(P);
     b.tile_begin.resize(P);
@@ -563,8 +568,6 @@ static int stage_preset_records(msg_ctx* ctx, Batch& b) {
 static int stage_event_records(msg_ctx* ctx, Batch& b) {
     using F32Lists = Batch::F32::Lists;
     Batch::F32& F = b.f32;
-    std::vector<F32Lists>& f32l = F.per_preset;
-    f32l.resize(F.presets.size());
     // Generator sharing (gen_share.h): the first event of the batch with a generator
     // key is its owner, and the only one on k_gen_normal's list; every event reads
     // its owner's micro slot.  One pass on this thread, before the records: the
@@ -596,47 +599,71 @@ static int stage_event_records(msg_ctx* ctx, Batch& b) {
             }
         }
     }
+    if ((size_t)b.nslots > ctx->h_spec_owner.size()) {
+        ctx->h_spec_owner.resize((size_t)b.nslots + b.nslots / 4);
+        ctx->h_spec_route.resize((size_t)b.nslots + b.nslots / 4);
+    }
+    int8_t* const route = ctx->h_spec_route.data();
     HostPool::get().run((int)F.presets.size(), [&](int i) {
         const int p = F.presets[i];
         const msg_preset& pr = b.presets[p];
         const PresetRt& r = b.prt[p];
-        F32Lists& L = f32l[i];
-        const double tilt = pr.gen_mode == MSG_GEN_FALLBACK ? -3.0 : pr.noise_tilt;
-        const double tilt_alpha = std::log(std::pow(10.0, tilt / 20.0)) / std::log(2.0);
-        const double env_tau = std::max(1e-6, (pr.micro_ms / 1000.0) * (pr.gen_mode == MSG_GEN_SKEWED ? 0.2 : 0.25));
+        const specshare::PresetConsts pc = specshare::preset_consts(pr);
         const int ne = b.info[p].n_events;
-        L.gen.reserve(ne);
         for (int k = 0; k < ne; ++k) {
             const int ei = b.slot_base[p] + k;
             const msg_event& e = ctx->h_events[ei];
             EventRt& x = b.ert[ei];
             memset(&x, 0, sizeof(x));
-            x.n = e.n;
-            x.gen_sr = e.gen_sr;
-            x.ops = spec_ops(pr, e);
-            x.cutoff_gen = e.cutoff_out * e.ufac;
-            x.roll = pr.bandlimit_roll_hz;
-            x.stretch = e.stretch;
-            x.tilt_alpha = tilt_alpha;
-            x.env_tau = env_tau;
-            x.warp_power = pr.nl_warp_power;
+            specshare::key_fields(pr, e, pc, x);
             const msg_event& oe = ctx->h_events[owner[ei]];
             x.micro_off = b.prt[oe.preset].pool_base + oe.pool_off;
             x.mlast_off = (k == ne - 1 && (x.ops & (SPEC_TILT_NOISE | SPEC_TILT_SKEW))) ? F.micro_last[p] : -1;
-            if (owner[ei] == ei) L.gen.push_back(ei);
+            // the kernel the event alone would run: part of its spectral key, so sharing
+            // never changes a grain's kernel
             const int ctp = (x.ops && b.use_ct) ? spectral_ct_plan(e.n) : -1;
             // k_spec3 reads the micro slot and writes the grain slot in 8-byte pairs: both offsets even
             if (b.use_s3 && x.ops &&
                 spec3_eligible(e.n, x.ops, x.gen_sr, x.cutoff_gen, x.roll, x.stretch,
                                (r.pool_base + e.pool_off) | x.micro_off,
                                &x.s3_kb, &x.s3_kz, &x.s3_ky, &x.s3_inv_f, &x.s3_pad))
-                L.s3.push_back(ei);
+                route[ei] = specshare::ROUTE_SPEC3;
             else if (ctp >= 0)
-                L.ct[ctp].push_back(ei);
-            else if (x.ops)
-                L.pending.push_back(ei);
+                route[ei] = (int8_t)(specshare::ROUTE_CT + ctp);
             else
-                L.small.push_back(ei);
+                route[ei] = x.ops ? specshare::ROUTE_RUNTIME : specshare::ROUTE_COPY;
+        }
+    });
+    // Spectral sharing (gen_share.h): the first event in list order with a spectral key
+    // runs the chain, and the overlap-add reads every event's grain from its owner's slot
+    // (grain_off).  One pass on this thread, in list order, as for the generator.
+    int32_t* const sown = ctx->h_spec_owner.data();
+    int64_t* const goff = ctx->h_grain_off.data();
+    {
+        std::vector<int32_t> nev(b.P);
+        for (int p = 0; p < b.P; ++p) nev[p] = b.info[p].n_events;
+        F.n_spec_runs = specshare::assign(b.ert, route, owner, F.presets.data(), (int)F.presets.size(),
+                                          b.slot_base.data(), nev.data(), b.nslots, ctx->sw.spec_share, sown,
+                                          ctx->spec_scratch);
+    }
+    // each preset's grain offsets and lists (owners only), presets in parallel again
+    std::vector<F32Lists>& f32l = F.per_preset;
+    f32l.resize(F.presets.size());
+    HostPool::get().run((int)F.presets.size(), [&](int i) {
+        const int p = F.presets[i];
+        F32Lists& L = f32l[i];
+        const int ne = b.info[p].n_events;
+        for (int k = 0; k < ne; ++k) {
+            const int ei = b.slot_base[p] + k;
+            const msg_event& se = ctx->h_events[sown[ei]];
+            goff[ei] = b.prt[se.preset].pool_base + se.pool_off;
+            if (owner[ei] == ei) L.gen.push_back(ei);
+            if (sown[ei] != ei) continue;
+            const int8_t rt = route[ei];
+            if (rt == specshare::ROUTE_SPEC3) L.s3.push_back(ei);
+            else if (rt >= specshare::ROUTE_CT) L.ct[rt - specshare::ROUTE_CT].push_back(ei);
+            else if (rt == specshare::ROUTE_RUNTIME) L.pending.push_back(ei);
+            else L.small.push_back(ei);
         }
     });
     for (F32Lists& L : f32l) {
@@ -644,7 +671,7 @@ static int stage_event_records(msg_ctx* ctx, Batch& b) {
         F.spec3.insert(F.spec3.end(), L.s3.begin(), L.s3.end());
         for (int c = 0; c < SPEC_CT_PLANS; ++c) F.ct[c].insert(F.ct[c].end(), L.ct[c].begin(), L.ct[c].end());
         F.spec_small.insert(F.spec_small.end(), L.small.begin(), L.small.end());
-        for (int ei : L.pending) {
+        for (int ei : L.pending) {   // no compile-time plan for the length: a runtime plan, planned on this thread
             EventRt& x = b.ert[ei];
             std::string why;
             const int pi = real_plan(ctx->grain_plans, x.n, why);
@@ -816,6 +843,7 @@ static int stage_upload(msg_ctx* ctx, Batch& b) {
         st.add(&ctx->er_cnt.p, ctx->h_er_cnt.data(), sizeof(int32_t) * b.ntaps);
     }
     st.add(&ctx->ert.p, b.ert, sizeof(EventRt) * b.nslots);
+    st.add(&ctx->grain_off.p, ctx->h_grain_off.data(), sizeof(int64_t) * b.nslots);
     add_vec(ctx->prt, b.prt);
     add_vec(ctx->gen_list, b.f32.gen_list);
     add_vec(ctx->spec_small, b.f32.spec_small);
@@ -962,8 +990,8 @@ static int enqueue_spectral(msg_ctx* ctx, Batch& b) {
 // Overlap-add x ADSR.
 static int enqueue_ola(msg_ctx* ctx, Batch& b) {
     if (b.tiles > 0) {
-        hipLaunchKernelGGL(k_ola_env, dim3((unsigned)b.tiles), dim3(OLA_T), 0, b.s, ctx->events.p, ctx->prt.p,
-                           ctx->tile_begin.p, b.P, ctx->grain.p, ctx->mono_a.p);
+        hipLaunchKernelGGL(k_ola_env, dim3((unsigned)b.tiles), dim3(OLA_T), 0, b.s, ctx->events.p, ctx->grain_off.p,
+                           ctx->prt.p, ctx->tile_begin.p, b.P, ctx->grain.p, ctx->mono_a.p);
         HIPCHK(ctx, hipGetLastError());
     }
     return MSG_OK;
@@ -993,7 +1021,8 @@ static int enqueue_fir(msg_ctx* ctx, Batch& b) {
             HIPCHK(ctx, fir8_counters(ctx, s));
             HIPCHK(ctx, launch_fir8p(nj, grid, s, ctx->prt.p, ctx->fir_jobs.p + F.job_off[i],
                                      ctx->d_fir4tab.p, ctx->hspec.p, ctx->mono_a.p, ctx->mono_y.p, ctx->fir8_ctr.p,
-                                     F.n_ola > 0 ? ctx->events.p : nullptr, ctx->grain.p, ctx->fir_lo.p));
+                                     F.n_ola > 0 ? ctx->events.p : nullptr, ctx->grain_off.p, ctx->grain.p,
+                                     ctx->fir_lo.p));
         } else if (i == 5)
             HIPCHK(ctx, launch_fir8(nj, s, ctx->prt.p, ctx->fir_jobs.p + F.job_off[i], ctx->d_fir4tab.p, ctx->hspec.p,
                                     ctx->mono_a.p, ctx->mono_y.p));
@@ -1077,7 +1106,7 @@ static int enqueue_stereo(msg_ctx* ctx, Batch& b) {
         if (b.fir.n_ola > 0) {   // the flagged ola_fir presets' mono a, which k_fir8p never wrote
             const int tmax = (int)((b.fir.ola_nmax + OLA_TILE - 1) / OLA_TILE);
             hipLaunchKernelGGL(k_ola_slots, dim3((unsigned)std::min<int64_t>((int64_t)S.cand * tmax, 1024)),
-                               dim3(OLA_T), 0, s, ctx->events.p, ctx->prt.p, ctx->f64_slot_preset.p,
+                               dim3(OLA_T), 0, s, ctx->events.p, ctx->grain_off.p, ctx->prt.p, ctx->f64_slot_preset.p,
                                ctx->f64_nslots.p, tmax, ctx->grain.p, ctx->mono_a.p);
             HIPCHK(ctx, hipGetLastError());
         }
@@ -1129,6 +1158,7 @@ static void host_clocks(msg_ctx* ctx, const Batch& b) {
     ctx->prof.ola_fir_sum += b.fir.n_ola;
     ctx->prof.gen_events_sum += (double)b.f32.n_events;
     ctx->prof.gen_grains_sum += (double)b.f32.n_owners;
+    ctx->prof.spec_runs_sum += (double)b.f32.n_spec_runs;
     ++ctx->prof.host_cnt;
 }
 

@@ -13,6 +13,7 @@
 #include "nprng.h"
 #include "plan.h"
 #include "fft_lds.h"
+#include "gen_share.h"
 
 #if defined(__HIPCC__)
 // x[i] of a uniform base with the byte offset formed in 32 bits, so the load or
@@ -87,9 +88,8 @@ struct EventRt {
     // behind the micro pool for the preset's last event, -1 for every other event
     int64_t mlast_off;
 };
-enum : int32_t {
-    SPEC_TILT_NOISE = 1, SPEC_TILT_SKEW = 2, SPEC_LOWPASS = 4, SPEC_STRETCH = 8, SPEC_WARP = 16,
-};
+// ops' SPEC_* bits are in gen_share.h, with spec_ops and the spectral key (the fields
+// above that the spectral kernels read), which the host-only build shares.
 
 // float64 grain chain (kernels_grain64.h): per-event and per-preset records
 struct Ev64 {

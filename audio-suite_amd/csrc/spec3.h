@@ -471,6 +471,9 @@ MSG_DEV void s3_chain(float2* buf, const float2* tab, const msg_event* __restric
         s3_rest<P>(buf, tab, ert, ev_list[li], off, grain_pool);
     }
 }
+// ev_list: the owners of the batch's spectral keys only (see k_spectral, kernels_spectral.h).
+// (One event per workgroup for an owners-only list shorter than two per CU measured
+// within noise of S3_EVENTS = 2 on C3: profiles/r09_specshare_s3events.jsonl.)
 template <class P>
 __global__ void __launch_bounds__(P::T)
 k_spec3(const msg_event* __restrict__ events, const EventRt* __restrict__ ert, const PresetRt* __restrict__ rt,

@@ -130,6 +130,7 @@ MSG_DEV void ct_rtransform(float2* buf, const float2* tab, bool inverse) {
     }
 }
 
+// ev_list: the owners of the batch's spectral keys only (see k_spectral, kernels_spectral.h).
 template <class P>
 __global__ void __launch_bounds__(P::T)
 k_spectral_ct(const msg_event* __restrict__ events, const EventRt* __restrict__ ert,

@@ -67,9 +67,10 @@ class Engine:
     def stage_times(self):
         """Per profiled batch: [0..9] stage times and [10..17] host clocks in ms, [18] presets
         whose overlap-add ran inside the FIR kernel, [19] float32-chain events, [20] the grains
-        the generator wrote for them (fewer when events share a generator stream)."""
-        arr = (C.c_float * 21)()
-        L.check(L.lib().msg_stage_times(self._ctx, arr, 21), self._ctx)
+        the generator wrote for them (fewer when events share a generator stream), [21] the
+        events among them that ran a spectral kernel (fewer when events share a spectral key)."""
+        arr = (C.c_float * 22)()
+        L.check(L.lib().msg_stage_times(self._ctx, arr, 22), self._ctx)
         return list(arr)
 
     def alloc_output(self, packed: PackedBatch):
