@@ -138,6 +138,7 @@ struct Batch {
         // micro pool, and per preset the offset msg_last_meta reads micro_last from
         int64_t n_events = 0, n_owners = 0;
         int64_t n_spec_runs = 0;                // events on a spectral list (specshare)
+        int64_t n_copy = 0;                     // those of spec_small without a spectral stage (copies)
         int64_t mlast_sum = 0;
         std::vector<int64_t> micro_last;
     } f32;

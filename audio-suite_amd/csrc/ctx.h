@@ -369,6 +369,7 @@ struct msg_ctx {
     std::vector<int8_t> h_spec_route;
     std::vector<int64_t> h_grain_off;
     specshare::Scratch spec_scratch;
+    int64_t h_spec_routes[MSG_ROUTE_COUNT] = {0};   // msg_last_spec_routes: spectral runs per kernel route
     int32_t last_n = 0;
 
     // What must come first and in this order; the members' destructors follow.

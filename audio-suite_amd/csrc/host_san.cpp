@@ -62,6 +62,7 @@ int msg_last_plan(msg_ctx*, msg_plan_info*, int32_t) { return no_device(); }
 int msg_last_events(msg_ctx*, int32_t, msg_event*, int32_t, int32_t*) { return no_device(); }
 int msg_last_meta(msg_ctx*, int32_t, double*, double*, int64_t, int64_t*) { return no_device(); }
 int msg_last_grain64(msg_ctx*, int32_t, int32_t, double*, int64_t, int64_t*) { return no_device(); }
+int msg_last_spec_routes(msg_ctx*, int64_t*, int32_t) { return no_device(); }
 int msg_set_profiling(msg_ctx*, int32_t) { return no_device(); }
 int msg_stage_times(msg_ctx*, float*, int32_t) { return no_device(); }
 int msg_gate(msg_ctx*, msg_ctx*, int32_t, int32_t) { return no_device(); }

@@ -1042,6 +1042,12 @@ int msg_last_grain64(msg_ctx* ctx, int32_t preset, int32_t k, double* grain, int
     return MSG_OK;
 }
 
+int msg_last_spec_routes(msg_ctx* ctx, int64_t* counts, int32_t n) {
+    if (!ctx || !counts || n < 0) return MSG_E_ARG;
+    for (int r = 0; r < n && r < MSG_ROUTE_COUNT; ++r) counts[r] = ctx->h_spec_routes[r];
+    return MSG_OK;
+}
+
 // The stages are in render_stages.h, in this order.
 int msg_render_batch(msg_ctx* ctx, const msg_preset* presets, int32_t P,
                      const double* bp_bank, int64_t bp_pairs, const double* const* irs, const int64_t* ir_lens, int32_t n_irs,

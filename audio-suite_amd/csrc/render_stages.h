@@ -671,6 +671,7 @@ static int stage_event_records(msg_ctx* ctx, Batch& b) {
         F.spec3.insert(F.spec3.end(), L.s3.begin(), L.s3.end());
         for (int c = 0; c < SPEC_CT_PLANS; ++c) F.ct[c].insert(F.ct[c].end(), L.ct[c].begin(), L.ct[c].end());
         F.spec_small.insert(F.spec_small.end(), L.small.begin(), L.small.end());
+        F.n_copy += (int64_t)L.small.size();
         for (int ei : L.pending) {   // no compile-time plan for the length: a runtime plan, planned on this thread
             EventRt& x = b.ert[ei];
             std::string why;
@@ -1170,5 +1171,13 @@ static void keep_mirrors(msg_ctx* ctx, const Batch& b) {
     ctx->h_ev64 = b.g64.ev;
     ctx->h_last64 = b.g64.last;
     ctx->h_micro_last = b.f32.micro_last;
+    static_assert(MSG_ROUTE_CT + SPEC_CT_PLANS == MSG_ROUTE_SPEC3, "msg_spec_route numbers the compile-time plans");
+    int64_t* const rc = ctx->h_spec_routes;
+    rc[MSG_ROUTE_COPY] = b.f32.n_copy;
+    rc[MSG_ROUTE_SMALL] = (int64_t)b.f32.spec_small.size() - b.f32.n_copy;
+    rc[MSG_ROUTE_BIG] = (int64_t)b.f32.spec_big.size();
+    for (int c = 0; c < SPEC_CT_PLANS; ++c) rc[MSG_ROUTE_CT + c] = (int64_t)b.f32.ct[c].size();
+    rc[MSG_ROUTE_SPEC3] = (int64_t)b.f32.spec3.size();
+    rc[MSG_ROUTE_F64] = (int64_t)b.g64.ev.size();
     ctx->last_n = b.P;
 }

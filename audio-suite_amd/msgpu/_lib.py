@@ -17,6 +17,10 @@ ABI_VERSION = 2
 # status codes (msg_status)
 MSG_OK, MSG_E_VALUE, MSG_E_UNSUPPORTED, MSG_E_DEVICE, MSG_E_ARG = 0, 1, 2, 3, 4
 
+# kernel routes of the spectral chain (msg_spec_route), in msg_last_spec_routes' order;
+# "ct<n>": the compile-time plan of n-sample grains
+SPEC_ROUTES = ("copy", "small", "big", "ct37500", "ct30000", "ct2400", "ct1920", "ct1500", "ct480", "spec3", "f64")
+
 # enums (msg_gen_mode, msg_process, msg_flag)
 GEN_MODE = {"Gaussian click": 0, "Dust impulses": 1, "Noise burst": 2, "Skewed transient": 3,
             "Resonant strike": 4, "Crackle / corona": 5, "Stick–slip friction": 6,
@@ -114,6 +118,7 @@ _PROTOS = {
                                 C.c_int64, C.POINTER(C.c_int64)]),
     "msg_last_grain64": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int64,
                                    C.POINTER(C.c_int64)]),
+    "msg_last_spec_routes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "msg_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),
     "msg_gate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "msg_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),

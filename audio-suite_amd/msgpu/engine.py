@@ -369,6 +369,13 @@ class Engine:
                                          C.byref(n)), self._ctx)
         return g[:n.value].copy()
 
+    def last_spec_routes(self):
+        """Spectral runs of the last batch per kernel route: {route name: count} over
+        _lib.SPEC_ROUTES (msg_last_spec_routes; host bookkeeping, no device work)."""
+        arr = (C.c_int64 * len(L.SPEC_ROUTES))()
+        L.check(L.lib().msg_last_spec_routes(self._ctx, arr, len(L.SPEC_ROUTES)), self._ctx)
+        return dict(zip(L.SPEC_ROUTES, (int(v) for v in arr)))
+
     def last_meta(self, preset: int, cap: int):
         micro = np.zeros(max(cap, 1), dtype=np.float64)
         grain = np.zeros(max(cap, 1), dtype=np.float64)

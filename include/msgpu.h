@@ -167,6 +167,22 @@ int msg_last_meta(msg_ctx* ctx, int32_t preset, double* micro, double* grain,
  * stage pins.  MSG_E_ARG for a float32-chain preset or k out of range. */
 int msg_last_grain64(msg_ctx* ctx, int32_t preset, int32_t k, double* grain, int64_t cap, int64_t* n);
 
+/* Kernel routes of the spectral chain.  A float32-chain event that runs the chain
+ * (the owner of its spectral key) runs exactly one of them:
+ *   COPY     no spectral stage: the generator's grain is copied
+ *   SMALL    k_spectral<256,8192>, runtime plan, up to 64 KiB of LDS
+ *   BIG      k_spectral<512,20480>, runtime plan, up to 160 KiB of LDS
+ *   CT + i   k_spectral_ct, compile-time plan i: grains of 37500, 30000, 2400,
+ *            1920, 1500 and 480 samples (MSGPU_SPEC_CT=0 sends them to SMALL / BIG)
+ *   SPEC3    k_spec3, the band-pruned 37500-sample kernel (MSGPU_SPEC3=0: CT + 0)
+ *   F64      the event belongs to a float64-chain preset (k_grain64) */
+enum msg_spec_route { MSG_ROUTE_COPY = 0, MSG_ROUTE_SMALL = 1, MSG_ROUTE_BIG = 2, MSG_ROUTE_CT = 3,
+                      MSG_ROUTE_SPEC3 = 9, MSG_ROUTE_F64 = 10, MSG_ROUTE_COUNT = 11 };
+/* Spectral runs of the last batch per route: counts[r] for r < min(n, MSG_ROUTE_COUNT),
+ * the lengths of the event lists the batch's kernels were launched over.  Host
+ * bookkeeping only: no device work, no synchronisation. */
+int msg_last_spec_routes(msg_ctx* ctx, int64_t* counts, int32_t n);
+
 /* Device time of each stage in ms (HIP events on the batch's stream),
  * averaged over the batches rendered since msg_set_profiling(ctx, 1):
  * [0] device plan + read-back, [1] host prep + uploads, [2] generate,
