@@ -371,6 +371,9 @@ struct msg_ctx {
     specshare::Scratch spec_scratch;
     int64_t h_spec_routes[MSG_ROUTE_COUNT] = {0};   // msg_last_spec_routes: spectral runs per kernel route
     int32_t last_n = 0;
+    // msg_quantize: signal extents, tile bases, stream keys and output offsets; per-tile partials
+    DevBuf<int64_t> pcm_meta;
+    DevBuf<int4> pcm_part;
 
     // What must come first and in this order; the members' destructors follow.
     ~msg_ctx() {

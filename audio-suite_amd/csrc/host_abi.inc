@@ -1,6 +1,7 @@
 // host_abi.inc — the host-side entry points of the C ABI (include/msgpu.h): the
 // render plan (plan.h), the NumPy stream primitives (nprng.h) and the host references
-// of the loudness and true-peak measurements (loudness.h, truepeak.h).  Included
+// of the loudness and true-peak measurements (loudness.h, truepeak.h) and of the PCM
+// quantiser (pcm.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables.
@@ -113,6 +114,22 @@ int msg_truepeak_host(const float* x, int32_t channels, int64_t n, int32_t sr, m
     if (sr < 1) return fail(nullptr, MSG_E_VALUE, "the sample rate must be positive");
     TruePeakRec r;
     tp_host(x, channels, n, sr, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// Fixed-point PCM of one signal in host memory: the definition of pcm.h word by word
+// (pcm_host), the device's bytes and record to the bit
+int msg_quantize_host(const float* x, int32_t channels, int64_t n, int32_t bits, int32_t dither, uint64_t seed,
+                      uint64_t key, void* out, msg_pcm_rec* rec) {
+    static_assert(sizeof(PcmRec) == sizeof(msg_pcm_rec), "PcmRec is msg_pcm_rec");
+    static_assert(PCM_DITHER_NONE == MSG_DITHER_NONE && PCM_DITHER_TPDF == MSG_DITHER_TPDF, "the dither codes");
+    if (!rec || n < 0 || (n > 0 && (!x || !out))) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    if (!pcm_bits_ok(bits)) return fail(nullptr, MSG_E_VALUE, "bits must be 16 or 24");
+    if (!pcm_dither_ok(dither)) return fail(nullptr, MSG_E_VALUE, "dither must be MSG_DITHER_NONE or MSG_DITHER_TPDF");
+    PcmRec r;
+    pcm_host(x, channels, n, bits, dither, seed, key, out, &r);
     std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }

@@ -3,7 +3,7 @@
 // (plan.h, msg_plan_host), the NumPy stream primitives (nprng.h, msg_rng_*) and
 // the host references of the render digest (digest.h, msg_digest_host) and of the
 // loudness and true-peak measurements (loudness.h, msg_loudness_host; truepeak.h,
-// msg_truepeak_host),
+// msg_truepeak_host) and of the PCM quantiser (pcm.h, msg_quantize_host),
 // compiled by g++ with -fsanitize=address,undefined into
 // msgpu/libmsgpu_hostsan.so.  The device entry points are stubs that fail with
 // MSG_E_DEVICE, so the ctypes binding (_lib.py) loads this library unchanged
@@ -23,6 +23,7 @@
 #include "digest.h"
 #include "loudness.h"
 #include "truepeak.h"
+#include "pcm.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -47,6 +48,7 @@ int64_t msg_sizeof(int32_t which) {
         case 3: return (int64_t)sizeof(msg_digest_rec);
         case 4: return (int64_t)sizeof(msg_loudness_rec);
         case 5: return (int64_t)sizeof(msg_truepeak_rec);
+        case 6: return (int64_t)sizeof(msg_pcm_rec);
         default: return -1;
     }
 }
@@ -96,6 +98,10 @@ int msg_truepeak(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*
 }
 int msg_truepeak_gain(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, msg_loudness_rec*,
                       msg_truepeak_rec*, double, double, double, void*) {
+    return no_device();
+}
+int msg_quantize(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, uint64_t,
+                 const uint64_t*, void*, const int64_t*, msg_pcm_rec*, void*) {
     return no_device();
 }
 // the digest's host reference (digest.h), the same code the product library runs

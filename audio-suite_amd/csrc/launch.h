@@ -206,3 +206,9 @@ hipError_t launch_truepeak(int n_sig, int channels, int os, unsigned tiles, hipS
 // x *= (float)g per signal, g from its records (loud_rec may be null); tiles of TP_GAIN_TILE frames
 hipError_t launch_truepeak_gain(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
                                 void* loud_rec, void* tp_rec, double target, double ceil_tp, double ceil_pk);
+
+// PCM quantiser (kernels_pcm.h): one workgroup per tile of PCM_TILE words, then one wave per
+// signal into rec (msg_pcm_rec records).  meta: offsets, frames, n_sig + 1 first tiles
+// (pcm_tiles of the words), stream keys, output byte offsets; part: one int4 per tile
+hipError_t launch_pcm(int n_sig, int channels, int bits, int dither, unsigned tiles, hipStream_t s, const float* x,
+                      const int64_t* meta, void* out, void* part, void* rec);

@@ -33,6 +33,7 @@
 #include "launch.h"
 #include "loudness.h"
 #include "truepeak.h"
+#include "pcm.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"
@@ -414,6 +415,7 @@ int64_t msg_sizeof(int32_t which) {
         case 3: return (int64_t)sizeof(msg_digest_rec);
         case 4: return (int64_t)sizeof(msg_loudness_rec);
         case 5: return (int64_t)sizeof(msg_truepeak_rec);
+        case 6: return (int64_t)sizeof(msg_pcm_rec);
         default: return -1;
     }
 }
@@ -959,6 +961,49 @@ int msg_truepeak_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_
     HIPCHK(ctx, hipMemcpyAsync(ctx->tp_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
     HIPCHK(ctx, launch_truepeak_gain(n_signals, channels, (unsigned)tiles, s, x_dev, ctx->tp_meta.p, loud_rec_dev,
                                      tp_rec_dev, loud_rec_dev ? target_lufs : 0.0, ceiling_tp, ceiling_peak));
+    HIPCHK(ctx, done.finish());
+    return MSG_OK;
+}
+
+int msg_quantize(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                 int32_t n_signals, int32_t bits, int32_t dither, uint64_t seed, const uint64_t* keys, void* out_dev,
+                 const int64_t* out_byte_off, msg_pcm_rec* rec_dev, void* stream) {
+    if (!ctx || !offsets || !n || !out_byte_off || !rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
+    if (!pcm_bits_ok(bits)) return fail(ctx, MSG_E_VALUE, "bits must be 16 or 24");
+    if (!pcm_dither_ok(dither)) return fail(ctx, MSG_E_VALUE, "dither must be MSG_DITHER_NONE or MSG_DITHER_TPDF");
+    if ((reinterpret_cast<uintptr_t>(x_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
+        return fail(ctx, MSG_E_ARG, "the input must be 4-byte and the output 16-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    std::vector<int64_t> meta;
+    const int64_t tiles = loud_meta(offsets, n, n_signals, [channels](int64_t f) { return pcm_tiles(f * channels); }, meta);
+    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
+    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many quantiser tiles");
+    if (tiles > 0 && (!x_dev || !out_dev)) return fail(ctx, MSG_E_ARG, "null buffer");
+    // the stream keys (formed here for both paths) and the output ranges: 16-byte aligned, disjoint
+    meta.resize((size_t)5 * n_signals + 1);
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    ranges.reserve((size_t)n_signals);
+    for (int i = 0; i < n_signals; ++i) {
+        const int64_t o = out_byte_off[i], b = pcm_bytes(n[i] * channels, bits);
+        if (o < 0 || (o & 15)) return fail(ctx, MSG_E_VALUE, "output offsets must be multiples of 16");
+        meta[(size_t)3 * n_signals + 1 + i] = (int64_t)pcm_stream_key(seed, keys ? keys[i] : (uint64_t)i);
+        meta[(size_t)4 * n_signals + 1 + i] = o;
+        if (b > 0) ranges.emplace_back(o, o + b);
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); ++i)
+        if (ranges[i].first < ranges[i - 1].second) return fail(ctx, MSG_E_VALUE, "output ranges overlap");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, stream_handover(ctx, s));
+    DoneGuard done(ctx, s);
+    HIPCHK(ctx, ctx->pcm_meta.ensure(meta.size()));
+    HIPCHK(ctx, ctx->pcm_part.ensure((size_t)std::max<int64_t>(1, tiles)));
+    // a pageable source is staged before hipMemcpyAsync returns (as msg_fir's uploads)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pcm_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, launch_pcm(n_signals, channels, bits, dither, (unsigned)tiles, s, x_dev, ctx->pcm_meta.p, out_dev,
+                           ctx->pcm_part.p, rec_dev));
     HIPCHK(ctx, done.finish());
     return MSG_OK;
 }

@@ -15,6 +15,7 @@ from .params import DEFAULTS, CONFIGS, config_params, merged  # noqa: F401
 from . import resample as _resample  # noqa: F401
 from . import loudness as _loudness  # noqa: F401  (the same for ``msgpu.loudness``)
 from . import truepeak as _truepeak  # noqa: F401
+from . import pcm as _pcm  # noqa: F401
 
 
 def render(params, progress=None, device: int = 0):
@@ -23,7 +24,8 @@ def render(params, progress=None, device: int = 0):
 
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
-                 out_lufs=None, out_ceiling=None, out_true_peak=None):
+                 out_lufs=None, out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf",
+                 out_dither_seed=0):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -36,7 +38,11 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     delivered rate and scaled in HBM (loudness.py; one device only), with
     ``out_ceiling`` a linear sample peak it may not exceed.  ``out_true_peak``: a
     ceiling in dBTP (BS.1770 true peak at the delivered rate, truepeak.py; one device
-    only), alone or with ``out_lufs`` / ``out_ceiling``; not with ``out_peak``."""
+    only), alone or with ``out_lufs`` / ``out_ceiling``; not with ``out_peak``.
+    ``out_bits``: 16 or 24, deliver fixed-point PCM quantised on the device after every
+    other rule (pcm.py; one device only): "audio" gives int16 / int32 arrays, "device"
+    views of the packed byte tensor; ``out_dither`` "tpdf" or "none", from the stream
+    (``out_dither_seed``, the preset's index in ``params_list``)."""
     if devices is not None and len(list(devices)) > 1:
         if out_sr is not None or out_peak is not None:
             raise NotImplementedError("out_sr on more than one device (multi.py sizes its shared memory by out_n)")
@@ -44,11 +50,16 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
             raise NotImplementedError("out_lufs on more than one device")
         if out_true_peak is not None:
             raise NotImplementedError("out_true_peak on more than one device")
+        if out_bits is not None:
+            raise NotImplementedError("out_bits on more than one device")
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)
     if devices is not None:
         device = int(list(devices)[0])
     from .dropin import render_batch as _rb
+    if out_bits is not None:
+        return _rb(params_list, device, results, out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits,
+                   out_dither, out_dither_seed)
     if out_true_peak is not None:
         return _rb(params_list, device, results, out_sr, out_peak, out_lufs, out_ceiling, out_true_peak)
     if out_lufs is not None or out_ceiling is not None:
@@ -105,11 +116,19 @@ def true_peak(x, sr, device: int = 0, db: bool = False):
     return _truepeak.true_peak(x, sr, device, db)
 
 
+def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0):
+    """x, (n,) or (n, 2) float32, as 16- or 24-bit PCM quantised on the device with TPDF
+    dither (or "none") from the stream (seed, key); see pcm.py.  NumPy in, int16 (or
+    int32 at 24 bits, sign-extended) out in x's shape; a device tensor in, the packed
+    device bytes out with no host synchronise."""
+    return _pcm.quantize(x, bits, dither, seed, key, device)
+
+
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0, devices=None, **kw):
     """The app's batch render (on_batch, MS:1524-1596); see batch.py.  ``devices``
     shards the variants across GPUs as render_batch does; ``export_sr`` /
     ``export_peak`` deliver the variants at another sample rate, ``export_lufs`` /
     ``export_ceiling`` at a BS.1770 integrated loudness, ``export_true_peak`` under a
-    ceiling in dBTP (one device)."""
+    ceiling in dBTP, ``export_bits`` as 16- or 24-bit PCM with TPDF dither (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

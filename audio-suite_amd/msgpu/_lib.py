@@ -95,6 +95,11 @@ class MsgTruePeakRec(C.Structure):
                 ("os", C.c_int32), ("pad", C.c_int32)]
 
 
+class MsgPcmRec(C.Structure):
+    _fields_ = [("clipped", C.c_int64), ("nan", C.c_int64), ("q_min", C.c_int32), ("q_max", C.c_int32),
+                ("bits", C.c_int32), ("dither", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -144,6 +149,11 @@ _PROTOS = {
     "msg_truepeak_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "msg_truepeak_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "msg_quantize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                               C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
+                               C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    "msg_quantize_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
+                                    C.c_void_p, C.c_void_p]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
@@ -181,7 +191,7 @@ def lib() -> C.CDLL:
             if L.msg_abi_version() != ABI_VERSION:
                 raise RuntimeError("libmsgpu ABI version mismatch")
             for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec, MsgLoudnessRec,
-                                        MsgTruePeakRec)):
+                                        MsgTruePeakRec, MsgPcmRec)):
                 if L.msg_sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmsgpu struct {st.__name__} size mismatch: "
                                        f"{L.msg_sizeof(which)} != {C.sizeof(st)}")

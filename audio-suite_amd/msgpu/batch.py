@@ -130,12 +130,14 @@ def _chunks(items, frames_of):
 
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0,
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
-                      export_lufs=None, export_ceiling=None, export_true_peak=None):
+                      export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
+                      export_dither="tpdf", export_dither_seed=0, export_records=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
     Returns a list of ``(name, audio, out_sr)`` in the reference's order (audio
-    (out_n, 2) float32); with ``folder``, also writes each as a float32 WAV.
+    (out_n, 2) float32); with ``folder``, also writes each as a float32 WAV
+    (with ``export_bits``: integer audio and integer-PCM WAVs, see below).
     ``progress(percent, text)`` gets the reference's status line per file.
 
     ``export_sr``: deliver the variants at that rate instead of ``base_sr``: each
@@ -155,6 +157,15 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     BS.1770-4 true peak, measured at the rate it is delivered at and held in HBM before
     the copy (truepeak.py); alone, or with ``export_lufs`` / ``export_ceiling``, one
     gain per variant from all of them.  Not together with ``export_peak``.  One device only.
+
+    ``export_bits``: 16 or 24, deliver fixed-point PCM: each variant is quantised on the
+    device after every level rule (pcm.py), with ``export_dither`` "tpdf" (or "none") from
+    the stream (``export_dither_seed``, the variant's index in the full seed x unfold x
+    stretch order, so the bits do not depend on how the batch is cut); the packed bytes
+    are what is copied to the host, the files are plain integer-PCM WAVs under the same
+    names, and the returned audio is the integer array in the file (int16, or int32 at
+    24 bits).  ``export_records``: a list that gets every variant's msg_pcm_rec
+    (pcm.PCM_DTYPE: clipped, nan, q_min, q_max, bits, dither) appended.  One device only.
     """
     from .pack import PackedBatch, out_frames
 
@@ -174,6 +185,12 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
         raise NotImplementedError("export_lufs on more than one device")
     if export_true_peak is not None and devices is not None and len(list(devices)) > 1:
         raise NotImplementedError("export_true_peak on more than one device")
+    if export_bits is not None:
+        from .pcm import check_bits, dither_code, records, unpack, write_wav_pcm
+        check_bits(export_bits)
+        dither_code(export_dither)
+        if devices is not None and len(list(devices)) > 1:
+            raise NotImplementedError("export_bits on more than one device")
     base = merged(base_params)
     pairs = variants(base, seeds, unfolds, stretches)
     keys = [key for key, _ in pairs]
@@ -184,7 +201,9 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
 
     def emit(key, audio):
         name = variant_name(*key, out_sr, names)
-        if folder is not None:
+        if folder is not None and export_bits is not None:
+            write_wav_pcm(os.path.join(folder, name), audio, out_sr, export_bits)
+        elif folder is not None:
             write_wav_float32(os.path.join(folder, name), audio, out_sr)
         results.append((name, audio, out_sr))
         if progress:
@@ -200,6 +219,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     from .engine import default_engine
     eng = default_engine(device)
     frames = out_frames(base)
+    done = 0                                         # variants before this chunk: the dither key's base
     for chunk in _chunks(keys, lambda k: frames):
         packed = PackedBatch.variants(base, chunk)   # the template packed once (MS:1578-1584)
         out = eng.render_packed(packed)
@@ -215,6 +235,18 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
         elif export_true_peak is not None:           # a ceiling alone
             from .dropin import truepeak_packed
             truepeak_packed(eng, out, offsets, lens, [out_sr] * len(chunk), export_true_peak, export_ceiling)
+        if export_bits is not None:                  # quantised last; the copy below is the byte tensor
+            from .dropin import quantize_packed
+            pcm, byte_off, nbytes, rec = quantize_packed(eng, out, offsets, lens, export_bits, export_dither,
+                                                         export_dither_seed, range(done, done + len(chunk)))
+            done += len(chunk)
+            eng.torch.cuda.synchronize(eng.device)
+            host = pcm.cpu().numpy()
+            if export_records is not None:
+                export_records.extend(records(rec))
+            for key, o, b, n in zip(chunk, byte_off, nbytes, lens):
+                emit(key, unpack(host[int(o):int(o) + int(b)], export_bits, (int(n), 2)))
+            continue
         eng.torch.cuda.synchronize(eng.device)
         host = out.cpu().numpy()
         for key, off, n in zip(chunk, offsets, lens):

@@ -185,6 +185,27 @@ def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak):
         truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling)
 
 
+def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=None):
+    """Renders lying in a device tensor (as loudness_packed) as ``bits``-bit PCM, quantised
+    and packed on the device after every level rule (msg_quantize, pcm.py): render i
+    takes its dither from the stream (seed, keys[i]).  Returns the device byte tensor,
+    each render's byte offset and length in it, and the device records (no host synchronise)."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    out, byte_off, rec = eng.quantize(y, offsets, lens, 2, bits, dither, seed, keys)
+    return out, byte_off, lens * (2 * (int(bits) // 8)), rec
+
+
+def _pcm_results(eng, y, offsets, lens, results, bits, dither, seed):
+    from .pcm import unpack
+    out, byte_off, nbytes, _ = quantize_packed(eng, y, offsets, lens, bits, dither, seed, range(len(lens)))
+    if results == "device":
+        return [out[int(o):int(o) + int(b)] for o, b in zip(byte_off, nbytes)]
+    eng.torch.cuda.synchronize(eng.device)
+    host = out.cpu().numpy()                     # the bytes cross, not the float32 renders
+    return [unpack(host[int(o):int(o) + int(b)], bits, (int(n), 2)) for o, b, n in zip(byte_off, nbytes, lens)]
+
+
 def _out_peaks(params_list, out_peak):
     if out_peak is None:
         return None
@@ -196,7 +217,7 @@ def _out_peaks(params_list, out_peak):
 
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
-                 out_ceiling=None, out_true_peak=None):
+                 out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -207,9 +228,18 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     and scaled in HBM (loudness_packed); ``out_ceiling``: a linear sample peak the scaled
     renders may not exceed.  ``out_true_peak``: a ceiling in dBTP (BS.1770 true peak at
     the delivered rate) they may not exceed, alone or with ``out_lufs`` / ``out_ceiling``
-    (truepeak_packed, loudness_packed)."""
+    (truepeak_packed, loudness_packed).  ``out_bits``: 16 or 24, deliver fixed-point PCM,
+    quantised last on the device (quantize_packed) with ``out_dither`` ("tpdf" or "none")
+    from the stream (``out_dither_seed``, the preset's index): int16 / int32 arrays
+    ("audio") or views of the packed byte tensor ("device")."""
     if results not in ("audio", "stats", "device"):
         raise ValueError("results must be 'audio', 'stats' or 'device'")
+    if out_bits is not None:
+        from .pcm import check_bits, dither_code
+        check_bits(out_bits)
+        dither_code(out_dither)
+        if results == "stats":
+            raise ValueError("out_bits applies to results 'audio' or 'device'")
     if out_true_peak is not None and out_peak is not None:
         raise ValueError("out_true_peak and out_peak are two level rules: give one")
     if out_true_peak is not None and results == "stats":
@@ -236,12 +266,16 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
                                            [merged(p)["base_sr"] for p in params_list], int(out_sr),
                                            _out_peaks(params_list, out_peak))
         _level(eng, y, y_off, y_lens, [int(out_sr)] * len(params_list), out_lufs, out_ceiling, out_true_peak)
+        if out_bits is not None:
+            return _pcm_results(eng, y, y_off, y_lens, results, out_bits, out_dither, out_dither_seed)
         parts = [y[int(o):int(o) + int(n)] for o, n in zip(y_off, y_lens)]
         if results == "device":
             return parts
         eng.torch.cuda.synchronize(eng.device)
         host = y.cpu().numpy()
         return [host[int(o):int(o) + int(n)].copy() for o, n in zip(y_off, y_lens)]
+    if out_bits is not None:
+        return _pcm_results(eng, out, packed.offsets, packed.out_n, results, out_bits, out_dither, out_dither_seed)
     if results == "device":
         return [out[int(o):int(o) + int(n)] for o, n in zip(packed.offsets, packed.out_n)]
     eng.torch.cuda.synchronize(eng.device)

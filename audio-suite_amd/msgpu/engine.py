@@ -347,6 +347,50 @@ class Engine:
                                               C.c_void_p(stream.cuda_stream)), self._ctx)
         return tp_rec
 
+    def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None):
+        """msg_quantize of signals lying in a device float32 tensor (as Engine.true_peak):
+        ``bits``-bit PCM (16 or 24) with ``dither`` ("tpdf" or "none") from the stream
+        (seed, keys[i]) (keys None: key = i), packed little-endian with no padding.
+        Returns ``(out, byte_offsets, rec)``: the device bytes (uint8; signal i at
+        byte_offsets[i], each rounded up to a multiple of 16; ``out``: a tensor to write
+        into instead of a new one), and the device records, an int64 tensor (signals, 4)
+        whose rows are msg_pcm_rec (pcm.records reads them on the host).  Enqueued on
+        ``stream``, no host synchronise."""
+        from .pcm import check_bits, dither_code
+        torch = self.torch
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        bits = check_bits(bits)
+        code = dither_code(dither)
+        n = int(off.size)
+        nbytes = cnt * (channels * (bits // 8))
+        byte_off = np.zeros(n, dtype=np.int64)
+        if n > 1:
+            byte_off[1:] = np.cumsum((nbytes[:-1] + 15) // 16 * 16)
+        total = int(byte_off[-1] + nbytes[-1]) if n else 0
+        if keys is None:
+            k = None
+        else:
+            k = np.ascontiguousarray([int(v) & 0xFFFFFFFFFFFFFFFF for v in keys], dtype=np.uint64)
+            if k.shape != off.shape:
+                raise ValueError("keys must have one entry per signal")
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=x.device)
+        elif (out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device or out.numel() < total or
+              out.data_ptr() % 16):
+            raise ValueError("out must be a contiguous 16-byte aligned uint8 tensor on x's device, large enough")
+        rec = torch.empty((n, 4), dtype=torch.int64, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        with self._lock:
+            L.check(L.lib().msg_quantize(self._ctx, C.c_void_p(x.data_ptr()), channels,
+                                         off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), n, bits, code,
+                                         C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                         None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         C.c_void_p(out.data_ptr()), byte_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         C.c_void_p(rec.data_ptr()), C.c_void_p(stream.cuda_stream)), self._ctx)
+        return out, byte_off, rec
+
     # ---- last-batch inspection -----------------------------------------
     def last_plan(self):
         arr = (L.MsgPlanInfo * self._last_n)()

@@ -16,6 +16,7 @@
  *   msg_resample     sample-rate conversion of renders in HBM     (no counterpart: SURVEY §0)
  *   msg_loudness     BS.1770 integrated loudness and LUFS gain in HBM (no counterpart)
  *   msg_truepeak     BS.1770 true peak and a dBTP ceiling in HBM   (no counterpart)
+ *   msg_quantize     16/24-bit PCM with TPDF dither, packed in HBM  (sf.write's subtype, MS:1589)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
 #ifndef MSGPU_H
@@ -117,7 +118,7 @@ int         msg_abi_version(void);
  * MSGPU_HOST_THREADS, else the CPU affinity / LOCAL_WORLD_SIZE, at most 16. */
 int         msg_host_threads(void);
 /* sizeof of the ABI structs (0 msg_preset, 1 msg_event, 2 msg_plan_info, 3 msg_digest_rec,
- * 4 msg_loudness_rec, 5 msg_truepeak_rec) for binding checks */
+ * 4 msg_loudness_rec, 5 msg_truepeak_rec, 6 msg_pcm_rec) for binding checks */
 int64_t     msg_sizeof(int32_t which);
 msg_ctx*    msg_create(int device_ordinal);
 void        msg_destroy(msg_ctx* ctx);
@@ -349,6 +350,40 @@ int msg_truepeak_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_
 /* The same definition as one loop over one signal in host memory (x: n frames of
  * `channels` interleaved words); needs no device. */
 int msg_truepeak_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_truepeak_rec* rec);
+
+/* Fixed-point PCM of signals lying in HBM, quantised and packed where they lie
+ * (csrc/pcm.h holds the definition, DESIGN.md §4e the kernel).  bits is 16 or 24,
+ * S = 2^(bits - 1); word w = frame channels + c of a signal becomes
+ *   q = clamp(rint((double)x S + d), -S, S - 1),  rint to nearest, ties to even,
+ * d = 0 for MSG_DITHER_NONE; for MSG_DITHER_TPDF the triangular dither
+ *   k = fmix64(seed ^ fmix64(key + G)),  h = fmix64(k + (w + 1) G),  G = 0x9E3779B97F4A7C15,
+ *   d = ((h & 0xFFFFFF) - ((h >> 32) & 0xFFFFFF)) 2^-24        (fmix64: MurmurHash3's finaliser),
+ * a function of (seed, key, w) alone: a signal's bytes do not depend on the batch it is
+ * quantised in.  Words are packed little-endian two's complement, 2 or 3 bytes each,
+ * with no padding; a signal writes exactly n channels bits / 8 bytes.
+ *   clipped    words whose rounded value lay outside [-S, S - 1] (+-inf included)
+ *   nan        NaN words; they write 0 and do not count in clipped
+ *   q_min/max  the least and greatest value written (0, 0 for an empty signal)
+ * Host and device agree to the bit, bytes and records. */
+enum msg_dither { MSG_DITHER_NONE = 0, MSG_DITHER_TPDF = 1 };
+typedef struct msg_pcm_rec {
+    int64_t clipped, nan;
+    int32_t q_min, q_max;
+    int32_t bits, dither;
+} msg_pcm_rec;
+/* Signals as for msg_truepeak (frame offsets and lengths into x_dev); signal i uses the
+ * stream (seed, keys[i]), keys == NULL: key = i, and is written from out_dev +
+ * out_byte_off[i].  out_dev and every out_byte_off[i] must be multiples of 16 and the
+ * ranges disjoint (MSG_E_VALUE); bits, dither or channels out of range: MSG_E_VALUE.
+ * rec_dev: n_signals device records.  Enqueued on stream with no host synchronise; one
+ * call in flight per context. */
+int msg_quantize(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                 int32_t n_signals, int32_t bits, int32_t dither, uint64_t seed, const uint64_t* keys,
+                 void* out_dev, const int64_t* out_byte_off, msg_pcm_rec* rec_dev, void* stream);
+/* The same definition as one loop over one signal in host memory (x: n frames of
+ * `channels` interleaved words; out: n channels bits / 8 bytes); needs no device. */
+int msg_quantize_host(const float* x, int32_t channels, int64_t n, int32_t bits, int32_t dither, uint64_t seed,
+                      uint64_t key, void* out, msg_pcm_rec* rec);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
