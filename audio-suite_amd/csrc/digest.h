@@ -17,7 +17,7 @@
 // The digest depends on every bit and on each word's position (fmix64 is a
 // bijection, so two words differ in k_j unless they are the same word at the
 // same place) and, being a sum, does not depend on the reduction order.  The
-// float64 sums are formed in a fixed order (kernels_digest.h; digest_host below
+// float64 sums are formed in a fixed order (kernels_digest.h; dg_host below
 // follows it step for step), so a render gives the same bits on any device and
 // on the host.
 //

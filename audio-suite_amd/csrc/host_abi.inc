@@ -1,10 +1,24 @@
-// host_abi.inc — the host-side entry points of the C ABI (include/msgpu.h): the
-// render plan (plan.h), the NumPy stream primitives (nprng.h) and the host references
-// of the loudness and true-peak measurements (loudness.h, truepeak.h) and of the PCM
-// quantiser (pcm.h).  Included
+// host_abi.inc — the host-side entry points of the C ABI (include/msgpu.h): the record
+// sizes (msg_sizeof), the render plan (plan.h), the NumPy stream primitives (nprng.h) and
+// the host references of the render digest (digest.h), of the loudness and true-peak
+// measurements (loudness.h, truepeak.h) and of the PCM quantiser (pcm.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
-// Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables.
+// Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
+// named above (DigestPart / dg_host, LoudRec / ld_host, TruePeakRec / tp_host, PcmRec / pcm_host).
+
+int64_t msg_sizeof(int32_t which) {
+    switch (which) {
+        case 0: return (int64_t)sizeof(msg_preset);
+        case 1: return (int64_t)sizeof(msg_event);
+        case 2: return (int64_t)sizeof(msg_plan_info);
+        case 3: return (int64_t)sizeof(msg_digest_rec);
+        case 4: return (int64_t)sizeof(msg_loudness_rec);
+        case 5: return (int64_t)sizeof(msg_truepeak_rec);
+        case 6: return (int64_t)sizeof(msg_pcm_rec);
+        default: return -1;
+    }
+}
 
 int msg_plan_host(const msg_preset* preset, const double* bp_bank, const double* ir_frag, int64_t ir_frag_len,
                   msg_plan_info* info, msg_event* events, int32_t max_events,
@@ -89,6 +103,16 @@ int msg_debug_spec_owners(const msg_preset* presets, int32_t n_presets, const ms
     const int64_t n = specshare::assign(rec.data(), route.data(), gown.data(), list.data(), n_presets, slot_base,
                                         n_events, n_slots, gen_share != 0 && spec_share != 0, owner, scratch);
     if (n_runs) *n_runs = n;
+    return MSG_OK;
+}
+
+// The render digest of one render in host memory: digest.h's fold in the device's order (dg_host)
+int msg_digest_host(const float* x, int64_t out_n, msg_digest_rec* rec) {
+    static_assert(sizeof(DigestPart) == sizeof(msg_digest_rec), "DigestPart is msg_digest_rec");
+    if (!rec || out_n < 0 || (out_n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    DigestPart r;
+    dg_host(x, out_n, &r);
+    std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }
 

@@ -40,18 +40,6 @@ int no_device() { return fail(nullptr, MSG_E_DEVICE, "host sanitizer build: no d
 extern "C" {
 int msg_abi_version(void) { return MSG_ABI_VERSION; }
 int msg_host_threads(void) { return HostPool::get().threads(); }
-int64_t msg_sizeof(int32_t which) {
-    switch (which) {
-        case 0: return (int64_t)sizeof(msg_preset);
-        case 1: return (int64_t)sizeof(msg_event);
-        case 2: return (int64_t)sizeof(msg_plan_info);
-        case 3: return (int64_t)sizeof(msg_digest_rec);
-        case 4: return (int64_t)sizeof(msg_loudness_rec);
-        case 5: return (int64_t)sizeof(msg_truepeak_rec);
-        case 6: return (int64_t)sizeof(msg_pcm_rec);
-        default: return -1;
-    }
-}
 const char* msg_last_error(msg_ctx*) { return g_err.c_str(); }
 msg_ctx* msg_create(int) { no_device(); return nullptr; }
 void msg_destroy(msg_ctx*) {}
@@ -103,15 +91,6 @@ int msg_truepeak_gain(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*,
 int msg_quantize(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, uint64_t,
                  const uint64_t*, void*, const int64_t*, msg_pcm_rec*, void*) {
     return no_device();
-}
-// the digest's host reference (digest.h), the same code the product library runs
-int msg_digest_host(const float* x, int64_t out_n, msg_digest_rec* rec) {
-    if (!rec || out_n < 0 || (out_n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
-    static_assert(sizeof(DigestPart) == sizeof(msg_digest_rec), "DigestPart is msg_digest_rec");
-    DigestPart r;
-    dg_host(x, out_n, &r);
-    std::memcpy(rec, &r, sizeof(r));
-    return MSG_OK;
 }
 #include "host_abi.inc"
 }  // extern "C"

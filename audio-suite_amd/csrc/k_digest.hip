@@ -1,6 +1,4 @@
-// k_digest.hip — translation unit of the per-render summary / digest (kernels_digest.h)
-// and the entry to its host reference (digest.h), which folds in the device's
-// order (bit-identical results).
+// k_digest.hip — translation unit of the per-render summary / digest (kernels_digest.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -23,9 +21,3 @@ hipError_t launch_digest(int n, int n_tiles, hipStream_t s, const float* out, co
 }
 
 int64_t digest_tiles(int64_t frames) { return dg_tiles(frames); }
-
-void digest_host(const float* x, int64_t frames, void* rec) {
-    DigestPart r;
-    dg_host(x, frames, &r);
-    std::memcpy(rec, &r, sizeof(r));
-}

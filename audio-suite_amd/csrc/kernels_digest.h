@@ -4,12 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "digest.h"
+#include "sig_tiles.h"
 
 MSG_DEV double dg_shfl(double v, int o) { return __shfl_xor(v, o, 64); }
-MSG_DEV uint64_t dg_shfl(uint64_t v, int o) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
+MSG_DEV uint64_t dg_shfl(uint64_t v, int o) { return sig_shfl64(v, o); }
 
 // the workgroup's fold: xor-butterfly in each wave (every lane ends with the
 // same value: each pair adds the same two operands), then waves 0..3 in order
@@ -38,7 +36,8 @@ k_digest_tiles(const float* __restrict__ out, const int64_t* __restrict__ frame_
                const int32_t* __restrict__ tile_base, int n, DigestPart* __restrict__ part) {
     __shared__ DigestPart lds[DG_T / 64];
     const int tile = blockIdx.x;
-    int lo = 0, hi = n;                              // the render holding this tile: last i with tile_base[i] <= tile
+    // the render holding this tile: sig_owner's search, written out (see sig_tiles.h)
+    int lo = 0, hi = n;
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (tile_base[mid] <= tile) lo = mid; else hi = mid;

@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "loudness.h"
+#include "sig_tiles.h"
 
 // out = M v + add, M 4 x 4 row-major (out may be v or add)
 MSG_DEV void ld_mv(const double* __restrict__ M, const double (&v)[4], const double (&add)[4], double (&out)[4]) {
@@ -42,13 +43,8 @@ struct LdTile {
 };
 MSG_DEV LdTile ld_locate(const int64_t* __restrict__ meta, int n_sig, int64_t hop, int tph, int64_t tile) {
     const int64_t* tile_base = meta + 2 * (int64_t)n_sig;
-    int lo = 0, hi = n_sig;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tile_base[mid] <= tile) lo = mid; else hi = mid;
-    }
     LdTile t;
-    t.p = __builtin_amdgcn_readfirstlane(lo);
+    t.p = sig_owner(tile_base, n_sig, tile);
     const int64_t n = meta[n_sig + t.p], tt = tile - tile_base[t.p];
     const int64_t h = tt / tph, ti = tt - h * tph;
     const int64_t hl = n - h * hop < hop ? n - h * hop : hop;
@@ -283,11 +279,6 @@ MSG_DEV double ld_block_z(const double* __restrict__ part, int64_t t0, int tph, 
     return (((hs[0] + hs[1]) + hs[2]) + hs[3]) / (4.0 * (double)hop);
 }
 
-MSG_DEV int64_t ld_shfl64(int64_t v, int o) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)((uint64_t)v >> 32), o, 64);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 // one wave per signal: lane i takes blocks i, i + 64, ... in order, then the xor-butterfly
 __global__ void __launch_bounds__(LD_GT)
 k_loud_gate(const int64_t* __restrict__ meta, int n_sig, int64_t hop, int tph, const double* __restrict__ part,
@@ -303,7 +294,7 @@ k_loud_gate(const int64_t* __restrict__ meta, int n_sig, int64_t hop, int tph, c
         if (ld_level(z) > -70.0) { s1 += z; ++c1; }
     }
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { s1 += __shfl_xor(s1, o, 64); c1 += ld_shfl64(c1, o); }
+    for (int o = 32; o >= 1; o >>= 1) { s1 += __shfl_xor(s1, o, 64); c1 += sig_shfl64(c1, o); }
     const double gate = c1 ? ld_level(s1 / (double)c1) - 10.0 : 0.0;
     if (c1)
         for (int64_t j = lane; j < nb; j += LD_GT) {
@@ -314,7 +305,7 @@ k_loud_gate(const int64_t* __restrict__ meta, int n_sig, int64_t hop, int tph, c
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         s2 += __shfl_xor(s2, o, 64);
-        c2 += ld_shfl64(c2, o);
+        c2 += sig_shfl64(c2, o);
         const double q = __shfl_xor(pk, o, 64);
         pk = pk > q ? pk : q;
     }
@@ -350,7 +341,7 @@ k_loud_gain(float* __restrict__ x, const int64_t* __restrict__ meta, int n_sig, 
         for (int q = threadIdx.x; q < n_sig; q += LD_T)
             if (tile_base[q + 1] == tile_base[q]) rec[q].gain = ld_gain_of(rec + q, target, ceiling);
     if (tile >= tile_base[n_sig]) return;
-    int lo = 0, hi = n_sig;
+    int lo = 0, hi = n_sig;                              // sig_owner's search, written out (see sig_tiles.h)
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (tile_base[mid] <= tile) lo = mid; else hi = mid;
@@ -358,22 +349,5 @@ k_loud_gain(float* __restrict__ x, const int64_t* __restrict__ meta, int n_sig, 
     const int p = __builtin_amdgcn_readfirstlane(lo);
     const double g = ld_gain_of(rec + p, target, ceiling);
     if (tile == tile_base[p] && threadIdx.x == 0) rec[p].gain = g;
-    const float gf = (float)g;
-    const int64_t n = meta[n_sig + p], f0 = (tile - tile_base[p]) * LD_GAIN_TILE;
-    float* xs = x + meta[p] * CH;
-#pragma unroll
-    for (int k = 0; k < LD_GAIN_PER; ++k) {
-        const int64_t f = f0 + k * LD_T + threadIdx.x;
-        if (f < n) {
-            if (CH == 2) {
-                typedef float v2f __attribute__((ext_vector_type(2)));
-                v2f* q = reinterpret_cast<v2f*>(xs) + f;
-                v2f w = *q;
-                w.x *= gf; w.y *= gf;
-                *q = w;
-            } else {
-                xs[f] *= gf;
-            }
-        }
-    }
+    sig_scale<CH, LD_T, LD_GAIN_PER>(x, meta, n_sig, p, tile, (float)g);
 }

@@ -16,25 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pcm.h"
-
-// Keeps four floats together as they were read (tp_pin of kernels_truepeak.h): a 16-byte
-// global load is not cut into the parts each later use needs.
-MSG_DEV void pcm_pin(float4& w) { asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w)); }
-
-// One 16-byte piece of a tile's span, as tp_piece of kernels_truepeak.h: local word e of
-// the span is float gbase + e of x, pieces are cut at 16-byte addresses, words outside
-// [0, E) read as zero and are never loaded; a piece wholly inside is one wide load, an
-// edge piece (odd mono offsets, the signal's end) loads float by float.  The caller
-// pins the piece (pcm_pin) once every load it wants in flight is issued.
-MSG_DEV float4 pcm_piece(const float* __restrict__ x, int64_t gbase, int e0, int E) {
-    float4 v;
-    if (e0 >= 0 && e0 + 4 <= E) return *reinterpret_cast<const float4*>(x + gbase + e0);
-    v.x = (e0 + 0 >= 0 && e0 + 0 < E) ? x[gbase + e0 + 0] : 0.0f;
-    v.y = (e0 + 1 >= 0 && e0 + 1 < E) ? x[gbase + e0 + 1] : 0.0f;
-    v.z = (e0 + 2 >= 0 && e0 + 2 < E) ? x[gbase + e0 + 2] : 0.0f;
-    v.w = (e0 + 3 >= 0 && e0 + 3 < E) ? x[gbase + e0 + 3] : 0.0f;
-    return v;
-}
+#include "sig_tiles.h"
 
 // Four consecutive words of one lane, the first m of them inside the signal, quantised
 // and packed as they lie in the file (arg: k + (w + 1) G of the first).
@@ -79,16 +61,6 @@ MSG_DEV void pcm_store4(const uint32_t pk[3], int m, unsigned char* __restrict__
     if (nb & 1) *tail = (unsigned char)last;
 }
 
-// the signal holding a tile: the last p with tile_base[p] <= tile (tp_signal)
-MSG_DEV int pcm_signal(const int64_t* __restrict__ tile_base, int n_sig, int64_t tile) {
-    int lo = 0, hi = n_sig;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tile_base[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
-
 MSG_DEV void pcm_acc_add(PcmAcc& a, const PcmAcc& b) {
     a.clipped += b.clipped;
     a.nan += b.nan;
@@ -105,7 +77,7 @@ k_pcm(const float* __restrict__ x, int channels, const int64_t* __restrict__ met
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t tile = blockIdx.x;
     const int64_t* tile_base = meta + 2 * (int64_t)n_sig;
-    const int p = pcm_signal(tile_base, n_sig, tile);
+    const int p = sig_owner(tile_base, n_sig, tile);
     const int64_t words = meta[n_sig + p] * channels;
     const int64_t w0 = (tile - tile_base[p]) * PCM_TILE;      // the tile's first word, 0 <= w0 < words
     const int64_t left = words - w0;
@@ -126,7 +98,7 @@ k_pcm(const float* __restrict__ x, int channels, const int64_t* __restrict__ met
         for (int t = 0; t < PCM_TURNS; ++t)
             v[t] = *reinterpret_cast<const float4*>(x + gbase + e_first + t * 256);
 #pragma unroll
-        for (int t = 0; t < PCM_TURNS; ++t) pcm_pin(v[t]);    // pinned once all are in flight: a pin waits for its load
+        for (int t = 0; t < PCM_TURNS; ++t) sig_pin(v[t]);    // pinned once all are in flight: a pin waits for its load
 #pragma unroll
         for (int t = 0; t < PCM_TURNS; ++t) {
             uint32_t pk[3];
@@ -147,9 +119,9 @@ k_pcm(const float* __restrict__ x, int channels, const int64_t* __restrict__ met
             u[t] = *reinterpret_cast<const float4*>(x + gbase + (ev + 8 > PCM_TILE ? ev : ev + 4));
         }
 #pragma unroll
-        for (int t = 0; t < PCM_TURNS; ++t) { pcm_pin(v[t]); pcm_pin(u[t]); }
-        if (e_first == 0) v[0] = pcm_piece(x, gbase, -a, E);
-        if (e_first + (PCM_TURNS - 1) * 256 + 4 == PCM_TILE) u[PCM_TURNS - 1] = pcm_piece(x, gbase, PCM_TILE - a, E);
+        for (int t = 0; t < PCM_TURNS; ++t) { sig_pin(v[t]); sig_pin(u[t]); }
+        if (e_first == 0) v[0] = sig_piece(x, gbase, -a, 0, E);
+        if (e_first + (PCM_TURNS - 1) * 256 + 4 == PCM_TILE) u[PCM_TURNS - 1] = sig_piece(x, gbase, PCM_TILE - a, 0, E);
 #pragma unroll
         for (int t = 0; t < PCM_TURNS; ++t) {
             uint32_t pk[3];
@@ -162,11 +134,11 @@ k_pcm(const float* __restrict__ x, int channels, const int64_t* __restrict__ met
         for (int t = 0; t < PCM_TURNS; ++t) {
             const int e0 = e_first + t * 256;
             if (e0 < E) {
-                float4 v = pcm_piece(x, gbase, e0 - a, E);
-                pcm_pin(v);
+                float4 v = sig_piece(x, gbase, e0 - a, 0, E);
+                sig_pin(v);
                 if (a != 0) {
-                    float4 u = pcm_piece(x, gbase, e0 - a + 4, E);
-                    pcm_pin(u);
+                    float4 u = sig_piece(x, gbase, e0 - a + 4, 0, E);
+                    sig_pin(u);
                     v = pcm_shifted(v, u, a);
                 }
                 const int m = E - e0 < 4 ? E - e0 : 4;        // words of the signal among the four

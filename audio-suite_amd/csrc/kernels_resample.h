@@ -7,9 +7,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "resample.h"
+#include "sig_tiles.h"
 
-// the signal that owns `tile`: the last one whose first tile is <= tile
-// (signals without output own no tile and are never the last such)
+// The signal that owns `tile`: the last one whose first tile is <= tile (signals without
+// output own no tile and are never the last such).  sig_owner's result by another form of
+// the search, kept because the resampler's kernels compile differently through sig_owner.
 __device__ inline int rs_signal(const int64_t* __restrict__ tile_base, int n_sig, int64_t tile) {
     int lo = 0, hi = n_sig - 1;
     while (lo < hi) {
@@ -18,27 +20,6 @@ __device__ inline int rs_signal(const int64_t* __restrict__ tile_base, int n_sig
     }
     return lo;
 }
-
-// One 16-byte piece of a tile's input span.  Local float e of the span is float
-// gbase + e of x (frames x channels); pieces are cut at 16-byte addresses, so
-// piece c holds local floats 4c - a .. 4c - a + 3.  Floats outside the signal,
-// [lo, hi) in local terms, read as zero; a piece wholly inside is one wide load,
-// an edge piece (odd mono offsets, odd frame offsets, the signal's ends) loads
-// float by float.
-__device__ inline float4 rs_piece(const float* __restrict__ x, int64_t gbase, int e0, int64_t lo, int64_t hi) {
-    if (e0 >= lo && e0 + 4 <= hi) return *reinterpret_cast<const float4*>(x + gbase + e0);
-    float4 v;
-    v.x = (e0 + 0 >= lo && e0 + 0 < hi) ? x[gbase + e0 + 0] : 0.0f;
-    v.y = (e0 + 1 >= lo && e0 + 1 < hi) ? x[gbase + e0 + 1] : 0.0f;
-    v.z = (e0 + 2 >= lo && e0 + 2 < hi) ? x[gbase + e0 + 2] : 0.0f;
-    v.w = (e0 + 3 >= lo && e0 + 3 < hi) ? x[gbase + e0 + 3] : 0.0f;
-    return v;
-}
-
-// Keeps a 16-byte LDS read whole: without it the compiler re-reads the window's
-// odd pairs from LDS (8-byte reads at a lane stride of 16 bytes, 4-way conflicts)
-// to feed packed FMAs instead of sliding it through registers.
-__device__ inline void rs_pin(float4& w) { asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w)); }
 
 // Integer decimation, up == 1.  Threads: RS_DTILE / RS_RB per channel.
 template <int DOWN, int CH>
@@ -61,7 +42,7 @@ k_resample_dec(const float* __restrict__ x, float* __restrict__ y, const int64_t
     const int64_t hi = (n - m_s) * CH < E ? (n - m_s) * CH : E;
     for (int c = tid; 4 * c - a < E; c += NT) {
         const int e0 = 4 * c - a;
-        const float4 v = rs_piece(x, gbase, e0, lo, hi);
+        const float4 v = sig_piece(x, gbase, e0, lo, hi);
         const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -80,12 +61,12 @@ k_resample_dec(const float* __restrict__ x, float* __restrict__ y, const int64_t
         const float4* row = rs_lds4 + (((ch * DOWN + r) * ROW + i0) >> 2);
         const float* tr = trow + r * A;                    // wave-uniform taps
         float4 w0 = row[0], w1;
-        rs_pin(w0);
+        sig_pin(w0);
         // four taps against the window w0 | w1; the two halves swap roles (A is a multiple of 8)
 #define RS_DEC_STEP(W0, W1, AT)                                                                                        \
         {                                                                                                              \
             W1 = row[((AT) >> 2) + 1];                                                                                 \
-            rs_pin(W1);                                                                                                \
+            sig_pin(W1);                                                                                                \
             const float t0 = tr[AT], t1 = tr[(AT) + 1], t2 = tr[(AT) + 2], t3 = tr[(AT) + 3];                          \
             acc0 = fmaf(t0, W0.x, acc0); acc1 = fmaf(t0, W0.y, acc1); acc2 = fmaf(t0, W0.z, acc2); acc3 = fmaf(t0, W0.w, acc3); \
             acc0 = fmaf(t1, W0.y, acc0); acc1 = fmaf(t1, W0.z, acc1); acc2 = fmaf(t1, W0.w, acc2); acc3 = fmaf(t1, W1.x, acc3); \
@@ -131,7 +112,7 @@ k_resample_gen(const float* __restrict__ x, float* __restrict__ y, const int64_t
     const int64_t lo = m_s < 0 ? -m_s * CH : 0;
     const int64_t hi = (n - m_s) * CH < E ? (n - m_s) * CH : E;
     // local float e lies at X[e + a]: piece c is the aligned float4 X[4c .. 4c + 3]
-    for (int c = tid; 4 * c - a < E; c += RS_LANES) rs_lds4[c] = rs_piece(x, gbase, 4 * c - a, lo, hi);
+    for (int c = tid; 4 * c - a < E; c += RS_LANES) rs_lds4[c] = sig_piece(x, gbase, 4 * c - a, lo, hi);
     __syncthreads();
     const int64_t n_out = rs_out_len(n, up, down);
     for (int l = tid; l < L; l += RS_LANES) {

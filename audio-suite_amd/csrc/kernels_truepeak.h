@@ -16,42 +16,9 @@
 #include <hip/hip_runtime.h>
 #include "truepeak.h"
 #include "loudness.h"
-
-// Keeps four floats together as they were read (rs_pin of kernels_resample.h): a 16-byte
-// LDS read stays one ds_read_b128 whose window slides through registers, and a 16-byte
-// global load is not cut into the parts each later use needs.
-MSG_DEV void tp_pin(float4& w) { asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w)); }
-
-// One 16-byte piece of a tile's span, as the resampler's rs_piece: local float e of the
-// span is float gbase + e of x, pieces are cut at 16-byte addresses, floats outside
-// [lo, hi) read as zero and are never loaded; a piece wholly inside is one wide load, an
-// edge piece (odd mono offsets, the signal's ends) loads float by float.
-MSG_DEV float4 tp_piece(const float* __restrict__ x, int64_t gbase, int e0, int64_t lo, int64_t hi) {
-    float4 v;
-    if (e0 >= lo && e0 + 4 <= hi) {
-        v = *reinterpret_cast<const float4*>(x + gbase + e0);
-        tp_pin(v);
-        return v;
-    }
-    v.x = (e0 + 0 >= lo && e0 + 0 < hi) ? x[gbase + e0 + 0] : 0.0f;
-    v.y = (e0 + 1 >= lo && e0 + 1 < hi) ? x[gbase + e0 + 1] : 0.0f;
-    v.z = (e0 + 2 >= lo && e0 + 2 < hi) ? x[gbase + e0 + 2] : 0.0f;
-    v.w = (e0 + 3 >= lo && e0 + 3 < hi) ? x[gbase + e0 + 3] : 0.0f;
-    return v;
-}
+#include "sig_tiles.h"
 
 MSG_DEV uint32_t tp_umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
-
-// the signal holding a tile: the last p with tile_base[p] <= tile (signals without a
-// tile share their successor's first tile and are never that one)
-MSG_DEV int tp_signal(const int64_t* __restrict__ tile_base, int n_sig, int64_t tile) {
-    int lo = 0, hi = n_sig;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tile_base[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
 
 template <int CH, int OS>
 __global__ void __launch_bounds__(TP_T)
@@ -62,7 +29,7 @@ k_truepeak(const float* __restrict__ x, const int64_t* __restrict__ meta, int n_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t tile = blockIdx.x;
     const int64_t* tile_base = meta + 2 * (int64_t)n_sig;
-    const int p = tp_signal(tile_base, n_sig, tile);
+    const int p = sig_owner(tile_base, n_sig, tile);
     const int64_t off = meta[p], n = meta[n_sig + p];
     const int64_t f0 = (tile - tile_base[p]) * TP_TILE;   // first position m' and first frame, 0 <= f0 <= n
     uint32_t pk = 0, tp = 0;
@@ -72,7 +39,7 @@ k_truepeak(const float* __restrict__ x, const int64_t* __restrict__ meta, int n_
         const int64_t gbase = (off + f0) * CH;            // 64-bit from the buffer's base
         const int a = (int)(((int64_t)(reinterpret_cast<uintptr_t>(x) >> 2) + gbase) & 3);
         for (int c = tid; 4 * c - a < E; c += TP_T) {
-            const float4 v = tp_piece(x, gbase, 4 * c - a, 0, E);
+            const float4 v = sig_piece<true, int64_t>(x, gbase, 4 * c - a, 0, E);
             pk = tp_umax(tp_umax(pk, tp_abs_bits(v.x)), tp_abs_bits(v.y));
             pk = tp_umax(tp_umax(pk, tp_abs_bits(v.z)), tp_abs_bits(v.w));
         }
@@ -86,7 +53,7 @@ k_truepeak(const float* __restrict__ x, const int64_t* __restrict__ meta, int n_
         const int64_t hi = (n - m_s) * CH < E ? (n - m_s) * CH : E;
         for (int c = tid; 4 * c - a < E; c += TP_T) {
             const int e0 = 4 * c - a;
-            const float4 v = tp_piece(x, gbase, e0, lo, hi);
+            const float4 v = sig_piece<true>(x, gbase, e0, lo, hi);
             const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -111,7 +78,7 @@ k_truepeak(const float* __restrict__ x, const int64_t* __restrict__ meta, int n_
 #pragma unroll
             for (int k = 0; k < 7; ++k) {
                 float4 v = row[k];
-                tp_pin(v);
+                sig_pin(v);
                 w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
             }
 #pragma unroll
@@ -204,28 +171,11 @@ k_truepeak_gain(float* __restrict__ x, const int64_t* __restrict__ meta, int n_s
                 if (lrec) lrec[q].gain = g;
             }
     if (tile >= tile_base[n_sig]) return;
-    const int p = tp_signal(tile_base, n_sig, tile);
+    const int p = sig_owner(tile_base, n_sig, tile);
     const double g = tp_gain_of(lrec ? lrec + p : nullptr, trec + p, target, ceil_tp, ceil_pk);
     if (tile == tile_base[p] && threadIdx.x == 0) {
         trec[p].gain = g;
         if (lrec) lrec[p].gain = g;
     }
-    const float gf = (float)g;
-    const int64_t n = meta[n_sig + p], f0 = (tile - tile_base[p]) * TP_GAIN_TILE;
-    float* xs = x + meta[p] * CH;                        // 64-bit from the buffer's base
-#pragma unroll
-    for (int k = 0; k < TP_GAIN_PER; ++k) {
-        const int64_t f = f0 + k * TP_T + threadIdx.x;
-        if (f < n) {
-            if (CH == 2) {
-                typedef float v2f __attribute__((ext_vector_type(2)));
-                v2f* q = reinterpret_cast<v2f*>(xs) + f;
-                v2f w = *q;
-                w.x *= gf; w.y *= gf;
-                *q = w;
-            } else {
-                xs[f] *= gf;
-            }
-        }
-    }
+    sig_scale<CH, TP_T, TP_GAIN_PER>(x, meta, n_sig, p, tile, (float)g);
 }

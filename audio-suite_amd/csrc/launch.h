@@ -176,11 +176,10 @@ hipError_t launch_stft64(unsigned frames, int lds_bytes, hipStream_t s, const Re
 
 // per-render summary and digest (kernels_digest.h): tiles of 2048 frames, then
 // one fold per render into res (msg_digest_rec records); part holds one
-// 48-byte partial per tile.  digest_host: the same fold on the host.
+// 48-byte partial per tile.
 hipError_t launch_digest(int n, int n_tiles, hipStream_t s, const float* out, const int64_t* frame_off,
                          const int64_t* frames, const int32_t* tile_base, void* part, void* res);
 int64_t digest_tiles(int64_t frames);
-void digest_host(const float* x, int64_t frames, void* rec);
 
 // polyphase resampler (kernels_resample.h): one workgroup per output tile of plan p;
 // meta holds four int64 rows of n_sig (input offsets, input frames, output offsets,

@@ -19,6 +19,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -31,6 +32,7 @@
 #include "fft_lds.h"
 #include "kernels_core.h"
 #include "launch.h"
+#include "digest.h"
 #include "loudness.h"
 #include "truepeak.h"
 #include "pcm.h"
@@ -246,22 +248,17 @@ static void choose_fir(int64_t M, int64_t n, int& N, int& P, int& Q, bool fir8, 
 
 using specshare::spec_ops;   // gen_share.h: shared with the host-only build
 
+static bool normal_driven(int gen_mode) {
+    return gen_mode == MSG_GEN_GAUSSIAN_CLICK || gen_mode == MSG_GEN_NOISE_BURST || gen_mode == MSG_GEN_SKEWED ||
+           gen_mode == MSG_GEN_RESONANT || gen_mode == MSG_GEN_FALLBACK;
+}
 // Presets whose grains run the float64 chain (kernels_grain64.h): the
 // generators outside the normal-driven closed forms, and every stage whose
 // reference result hinges on float64 magnitudes or noise floors.
 static bool is_precise(const msg_preset& p) {
     const uint32_t f64_stages = MSG_F_PARTIAL_LOCK | MSG_F_CEP_WARP | MSG_F_RES_BANK | MSG_F_WAVEGUIDE |
                                 MSG_F_EVENT_FEEDBACK | MSG_F_IMPRINT | MSG_F_MULTIBAND;
-    if (p.flags & f64_stages) return true;
-    switch (p.gen_mode) {
-        case MSG_GEN_GAUSSIAN_CLICK: case MSG_GEN_NOISE_BURST: case MSG_GEN_SKEWED:
-        case MSG_GEN_RESONANT: case MSG_GEN_FALLBACK: return false;
-        default: return true;
-    }
-}
-static bool normal_driven(int gen_mode) {
-    return gen_mode == MSG_GEN_GAUSSIAN_CLICK || gen_mode == MSG_GEN_NOISE_BURST || gen_mode == MSG_GEN_SKEWED ||
-           gen_mode == MSG_GEN_RESONANT || gen_mode == MSG_GEN_FALLBACK;
+    return (p.flags & f64_stages) || !normal_driven(p.gen_mode);
 }
 
 // Stages of the float64 chain one event runs, with the reference's own
@@ -383,42 +380,11 @@ static int sf_upload(msg_ctx* ctx, hipStream_t s, const std::vector<PresetRt>& p
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
-// rows of a loudness call's metadata: offsets, frames, then n + 1 first tiles
-// (tiles_of(frames) per signal); returns the tile count, or -1 on a bad extent
-template <class F>
-static int64_t loud_meta(const int64_t* offsets, const int64_t* n, int32_t n_signals, F tiles_of,
-                         std::vector<int64_t>& meta) {
-    meta.assign((size_t)3 * n_signals + 1, 0);
-    int64_t tiles = 0;
-    for (int i = 0; i < n_signals; ++i) {
-        if (n[i] < 0 || n[i] > MSG_MAX_FRAMES || offsets[i] < 0) return -1;
-        meta[i] = offsets[i];
-        meta[(size_t)n_signals + i] = n[i];
-        meta[(size_t)2 * n_signals + i] = tiles;
-        tiles += tiles_of(n[i]);
-    }
-    meta[(size_t)3 * n_signals] = tiles;
-    return tiles;
-}
-
 extern "C" {
 
 int msg_abi_version(void) { return MSG_ABI_VERSION; }
 
 int msg_host_threads(void) { return HostPool::get().threads(); }
-
-int64_t msg_sizeof(int32_t which) {
-    switch (which) {
-        case 0: return (int64_t)sizeof(msg_preset);
-        case 1: return (int64_t)sizeof(msg_event);
-        case 2: return (int64_t)sizeof(msg_plan_info);
-        case 3: return (int64_t)sizeof(msg_digest_rec);
-        case 4: return (int64_t)sizeof(msg_loudness_rec);
-        case 5: return (int64_t)sizeof(msg_truepeak_rec);
-        case 6: return (int64_t)sizeof(msg_pcm_rec);
-        default: return -1;
-    }
-}
 
 const char* msg_last_error(msg_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
 
@@ -754,265 +720,7 @@ int msg_fir(msg_ctx* ctx, const float* x_dev, float* y_dev, int64_t n, int32_t n
     return MSG_OK;
 }
 
-int msg_digest(msg_ctx* ctx, const float* out_dev, const int64_t* out_offsets, const int64_t* out_n,
-               int32_t n_renders, msg_digest_rec* rec_dev, void* stream) {
-    if (!ctx || !out_offsets || !out_n || !rec_dev || n_renders < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
-    if (n_renders == 0) return MSG_OK;
-    // rows: [0, n) frame offsets, [n, 2n) frames, then n + 1 tile bases (int32) in the same upload
-    std::vector<int64_t> meta((size_t)2 * n_renders + (n_renders + 2) / 2 + 1, 0);
-    int32_t* tb = reinterpret_cast<int32_t*>(meta.data() + 2 * (size_t)n_renders);
-    int64_t tiles = 0;
-    for (int i = 0; i < n_renders; ++i) {
-        if (out_n[i] < 0 || out_n[i] > MSG_MAX_FRAMES || out_offsets[i] < 0)
-            return fail(ctx, MSG_E_ARG, "bad render extent");
-        meta[i] = out_offsets[i];
-        meta[(size_t)n_renders + i] = out_n[i];
-        tb[i] = (int32_t)tiles;
-        tiles += digest_tiles(out_n[i]);
-        if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many digest tiles");
-    }
-    tb[n_renders] = (int32_t)tiles;
-    if (tiles > 0 && !out_dev) return fail(ctx, MSG_E_ARG, "null output buffer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, stream_handover(ctx, s));
-    DoneGuard done(ctx, s);
-    HIPCHK(ctx, ctx->dg_meta.ensure(meta.size()));
-    HIPCHK(ctx, ctx->dg_part.ensure((size_t)std::max<int64_t>(1, tiles) * sizeof(msg_digest_rec)));
-    // a pageable source is staged before hipMemcpyAsync returns (as msg_fir's uploads)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dg_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
-    const int64_t* dm = ctx->dg_meta.p;
-    HIPCHK(ctx, launch_digest(n_renders, (int)tiles, s, out_dev, dm, dm + n_renders,
-                              reinterpret_cast<const int32_t*>(dm + 2 * (size_t)n_renders), ctx->dg_part.p, rec_dev));
-    HIPCHK(ctx, done.finish());
-    return MSG_OK;
-}
-
-int msg_resample(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* in_offsets, const int64_t* in_n,
-                 int32_t n_signals, int32_t up, int32_t down, const double* h, int64_t K, float* y_dev,
-                 const int64_t* out_offsets, void* stream) {
-    if (!ctx || !x_dev || !y_dev || !in_offsets || !in_n || !out_offsets || n_signals < 0)
-        return fail(ctx, MSG_E_ARG, "bad arguments");
-    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
-    if (up < 1 || down < 1) return fail(ctx, MSG_E_VALUE, "the ratio must be positive");
-    if (up != down && (!h || K < 1 || (K & 1) == 0)) return fail(ctx, MSG_E_VALUE, "the tap count must be odd");
-    if (up > RS_RATIO_MAX || down > RS_RATIO_MAX)
-        return fail(ctx, MSG_E_UNSUPPORTED, "ratio beyond the resampler's limits");
-    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
-        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
-    if (n_signals == 0) return MSG_OK;
-    RsPlan plan{};
-    if (up != down) {
-        plan = rs_plan(up, down, K, channels);
-        if (plan.kind < 0) return fail(ctx, MSG_E_UNSUPPORTED, "ratio beyond the resampler's tap-table or LDS limit");
-    }
-    // rows: input offsets, input frames, output offsets, first tiles
-    std::vector<int64_t> meta((size_t)4 * n_signals);
-    int64_t tiles = 0, x_end = 0, y_end = 0;
-    for (int i = 0; i < n_signals; ++i) {
-        if (in_n[i] < 0 || in_n[i] > MSG_MAX_FRAMES || in_offsets[i] < 0 || out_offsets[i] < 0)
-            return fail(ctx, MSG_E_ARG, "bad signal extent");
-        const int64_t n_out = rs_out_len(in_n[i], up, down);
-        if (n_out > MSG_MAX_FRAMES) return fail(ctx, MSG_E_UNSUPPORTED, "output longer than 2^31 - 2^20 frames");
-        meta[i] = in_offsets[i];
-        meta[(size_t)n_signals + i] = in_n[i];
-        meta[(size_t)2 * n_signals + i] = out_offsets[i];
-        meta[(size_t)3 * n_signals + i] = tiles;
-        if (up != down) tiles += (n_out + plan.tile - 1) / plan.tile;
-        x_end = std::max(x_end, in_offsets[i] + in_n[i]);
-        y_end = std::max(y_end, out_offsets[i] + n_out);
-    }
-    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many output tiles");
-    if (x_dev < y_dev + y_end * channels && y_dev < x_dev + x_end * channels)
-        return fail(ctx, MSG_E_ARG, "x and y must not alias");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, stream_handover(ctx, s));
-    DoneGuard done(ctx, s);
-    if (up == down) {                                       // a copy
-        for (int i = 0; i < n_signals; ++i)
-            if (in_n[i] > 0)
-                HIPCHK(ctx, hipMemcpyAsync(y_dev + out_offsets[i] * channels, x_dev + in_offsets[i] * channels,
-                                           sizeof(float) * (size_t)(in_n[i] * channels), hipMemcpyDeviceToDevice, s));
-        HIPCHK(ctx, done.finish());
-        return MSG_OK;
-    }
-    if (tiles == 0) { HIPCHK(ctx, done.finish()); return MSG_OK; }
-    std::vector<float> tab((size_t)plan.tab);
-    rs_table(plan, up, down, h, K, tab.data());
-    HIPCHK(ctx, ctx->rs_meta.ensure(meta.size()));
-    HIPCHK(ctx, ctx->rs_tab.ensure(tab.size()));
-    // pageable sources are staged before hipMemcpyAsync returns (as msg_fir's uploads)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rs_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rs_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, launch_resample(plan, channels, (unsigned)tiles, s, x_dev, y_dev, ctx->rs_meta.p, n_signals,
-                                ctx->rs_tab.p, up, down, K));
-    HIPCHK(ctx, done.finish());
-    return MSG_OK;
-}
-
-int msg_loudness(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
-                 int32_t n_signals, int32_t sr, msg_loudness_rec* rec_dev, void* stream) {
-    if (!ctx || !offsets || !n || !rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
-    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
-    if (!ld_rate_ok(sr)) return fail(ctx, MSG_E_VALUE, "the sample rate must be a multiple of 10, at least 4000");
-    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
-        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
-    if (n_signals == 0) return MSG_OK;
-    const int64_t hop = sr / 10;
-    std::vector<int64_t> meta;
-    const int64_t tiles = loud_meta(offsets, n, n_signals, [hop](int64_t f) { return ld_tiles(f, hop); }, meta);
-    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
-    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many loudness tiles");
-    if (tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
-    std::vector<double> tab(LD_TAB_N);
-    ld_table(sr, tab.data());
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, stream_handover(ctx, s));
-    DoneGuard done(ctx, s);
-    HIPCHK(ctx, ctx->ld_meta.ensure(meta.size()));
-    HIPCHK(ctx, ctx->ld_tab.ensure(tab.size()));
-    HIPCHK(ctx, ctx->ld_state.ensure((size_t)std::max<int64_t>(1, tiles) * 4 * channels));
-    HIPCHK(ctx, ctx->ld_part.ensure((size_t)std::max<int64_t>(1, tiles) * 2));
-    // pageable sources are staged before hipMemcpyAsync returns (as msg_fir's uploads)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ld_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ld_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, launch_loudness(n_signals, channels, (unsigned)tiles, s, x_dev, ctx->ld_meta.p, hop, ctx->ld_tab.p,
-                                ctx->ld_state.p, ctx->ld_part.p, rec_dev));
-    HIPCHK(ctx, done.finish());
-    return MSG_OK;
-}
-
-int msg_loudness_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
-                      int32_t n_signals, msg_loudness_rec* rec_dev, double target_lufs, double ceiling, void* stream) {
-    if (!ctx || !offsets || !n || !rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
-    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
-    if (!std::isfinite(target_lufs) || std::isnan(ceiling)) return fail(ctx, MSG_E_VALUE, "target and ceiling must be numbers");
-    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
-        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
-    if (n_signals == 0) return MSG_OK;
-    std::vector<int64_t> meta;
-    const int64_t tiles = loud_meta(offsets, n, n_signals,
-                                    [](int64_t f) { return (f + LD_GAIN_TILE - 1) / LD_GAIN_TILE; }, meta);
-    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
-    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many gain tiles");
-    if (tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, stream_handover(ctx, s));
-    DoneGuard done(ctx, s);
-    HIPCHK(ctx, ctx->ld_meta.ensure(meta.size()));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ld_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, launch_loudness_gain(n_signals, channels, (unsigned)tiles, s, x_dev, ctx->ld_meta.p, rec_dev, target_lufs,
-                                     ceiling));
-    HIPCHK(ctx, done.finish());
-    return MSG_OK;
-}
-
-int msg_truepeak(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
-                 int32_t n_signals, int32_t sr, msg_truepeak_rec* rec_dev, void* stream) {
-    if (!ctx || !offsets || !n || !rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
-    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
-    if (sr < 1) return fail(ctx, MSG_E_VALUE, "the sample rate must be positive");
-    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
-        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
-    if (n_signals == 0) return MSG_OK;
-    std::vector<int64_t> meta;
-    const int64_t tiles = loud_meta(offsets, n, n_signals, [](int64_t f) { return tp_tiles(f); }, meta);
-    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
-    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many true-peak tiles");
-    if (tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, stream_handover(ctx, s));
-    DoneGuard done(ctx, s);
-    HIPCHK(ctx, ctx->tp_meta.ensure(meta.size()));
-    HIPCHK(ctx, ctx->tp_part.ensure((size_t)std::max<int64_t>(1, tiles)));
-    // a pageable source is staged before hipMemcpyAsync returns (as msg_fir's uploads)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->tp_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, launch_truepeak(n_signals, channels, tp_os(sr), (unsigned)tiles, s, x_dev, ctx->tp_meta.p,
-                                ctx->d_tp_tab.p, ctx->tp_part.p, rec_dev));
-    HIPCHK(ctx, done.finish());
-    return MSG_OK;
-}
-
-int msg_truepeak_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
-                      int32_t n_signals, msg_loudness_rec* loud_rec_dev, msg_truepeak_rec* tp_rec_dev,
-                      double target_lufs, double ceiling_tp, double ceiling_peak, void* stream) {
-    if (!ctx || !offsets || !n || !tp_rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
-    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
-    if ((loud_rec_dev && !std::isfinite(target_lufs)) || std::isnan(ceiling_tp) || std::isnan(ceiling_peak))
-        return fail(ctx, MSG_E_VALUE, "target and ceilings must be numbers");
-    if (channels == 2 && (reinterpret_cast<uintptr_t>(x_dev) & 7))
-        return fail(ctx, MSG_E_ARG, "stereo input must be 8-byte aligned");
-    if (n_signals == 0) return MSG_OK;
-    std::vector<int64_t> meta;
-    const int64_t tiles = loud_meta(offsets, n, n_signals,
-                                    [](int64_t f) { return (f + TP_GAIN_TILE - 1) / TP_GAIN_TILE; }, meta);
-    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
-    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many gain tiles");
-    if (tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, stream_handover(ctx, s));
-    DoneGuard done(ctx, s);
-    HIPCHK(ctx, ctx->tp_meta.ensure(meta.size()));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->tp_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, launch_truepeak_gain(n_signals, channels, (unsigned)tiles, s, x_dev, ctx->tp_meta.p, loud_rec_dev,
-                                     tp_rec_dev, loud_rec_dev ? target_lufs : 0.0, ceiling_tp, ceiling_peak));
-    HIPCHK(ctx, done.finish());
-    return MSG_OK;
-}
-
-int msg_quantize(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
-                 int32_t n_signals, int32_t bits, int32_t dither, uint64_t seed, const uint64_t* keys, void* out_dev,
-                 const int64_t* out_byte_off, msg_pcm_rec* rec_dev, void* stream) {
-    if (!ctx || !offsets || !n || !out_byte_off || !rec_dev || n_signals < 0) return fail(ctx, MSG_E_ARG, "bad arguments");
-    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
-    if (!pcm_bits_ok(bits)) return fail(ctx, MSG_E_VALUE, "bits must be 16 or 24");
-    if (!pcm_dither_ok(dither)) return fail(ctx, MSG_E_VALUE, "dither must be MSG_DITHER_NONE or MSG_DITHER_TPDF");
-    if ((reinterpret_cast<uintptr_t>(x_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
-        return fail(ctx, MSG_E_ARG, "the input must be 4-byte and the output 16-byte aligned");
-    if (n_signals == 0) return MSG_OK;
-    std::vector<int64_t> meta;
-    const int64_t tiles = loud_meta(offsets, n, n_signals, [channels](int64_t f) { return pcm_tiles(f * channels); }, meta);
-    if (tiles < 0) return fail(ctx, MSG_E_ARG, "bad signal extent");
-    if (tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many quantiser tiles");
-    if (tiles > 0 && (!x_dev || !out_dev)) return fail(ctx, MSG_E_ARG, "null buffer");
-    // the stream keys (formed here for both paths) and the output ranges: 16-byte aligned, disjoint
-    meta.resize((size_t)5 * n_signals + 1);
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    ranges.reserve((size_t)n_signals);
-    for (int i = 0; i < n_signals; ++i) {
-        const int64_t o = out_byte_off[i], b = pcm_bytes(n[i] * channels, bits);
-        if (o < 0 || (o & 15)) return fail(ctx, MSG_E_VALUE, "output offsets must be multiples of 16");
-        meta[(size_t)3 * n_signals + 1 + i] = (int64_t)pcm_stream_key(seed, keys ? keys[i] : (uint64_t)i);
-        meta[(size_t)4 * n_signals + 1 + i] = o;
-        if (b > 0) ranges.emplace_back(o, o + b);
-    }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); ++i)
-        if (ranges[i].first < ranges[i - 1].second) return fail(ctx, MSG_E_VALUE, "output ranges overlap");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, stream_handover(ctx, s));
-    DoneGuard done(ctx, s);
-    HIPCHK(ctx, ctx->pcm_meta.ensure(meta.size()));
-    HIPCHK(ctx, ctx->pcm_part.ensure((size_t)std::max<int64_t>(1, tiles)));
-    // a pageable source is staged before hipMemcpyAsync returns (as msg_fir's uploads)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pcm_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, launch_pcm(n_signals, channels, bits, dither, (unsigned)tiles, s, x_dev, ctx->pcm_meta.p, out_dev,
-                           ctx->pcm_part.p, rec_dev));
-    HIPCHK(ctx, done.finish());
-    return MSG_OK;
-}
-
-int msg_digest_host(const float* x, int64_t out_n, msg_digest_rec* rec) {
-    if (!rec || out_n < 0 || (out_n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
-    digest_host(x, out_n, rec);
-    return MSG_OK;
-}
+#include "signal_abi.inc"
 
 int msg_last_plan(msg_ctx* ctx, msg_plan_info* info, int32_t n_presets) {
     if (!ctx || !info) return MSG_E_ARG;

@@ -44,29 +44,17 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     views of the packed byte tensor; ``out_dither`` "tpdf" or "none", from the stream
     (``out_dither_seed``, the preset's index in ``params_list``)."""
     if devices is not None and len(list(devices)) > 1:
-        if out_sr is not None or out_peak is not None:
-            raise NotImplementedError("out_sr on more than one device (multi.py sizes its shared memory by out_n)")
-        if out_lufs is not None or out_ceiling is not None:
-            raise NotImplementedError("out_lufs on more than one device")
-        if out_true_peak is not None:
-            raise NotImplementedError("out_true_peak on more than one device")
-        if out_bits is not None:
-            raise NotImplementedError("out_bits on more than one device")
+        from .export import Delivery
+        Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits).one_device(
+            "out_", len(list(devices)), companions=True)
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)
     if devices is not None:
         device = int(list(devices)[0])
     from .dropin import render_batch as _rb
-    if out_bits is not None:
-        return _rb(params_list, device, results, out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits,
-                   out_dither, out_dither_seed)
-    if out_true_peak is not None:
-        return _rb(params_list, device, results, out_sr, out_peak, out_lufs, out_ceiling, out_true_peak)
-    if out_lufs is not None or out_ceiling is not None:
-        return _rb(params_list, device, results, out_sr, out_peak, out_lufs, out_ceiling)
-    if out_sr is None and out_peak is None:
-        return _rb(params_list, device, results)
-    return _rb(params_list, device, results, out_sr, out_peak)
+    return _rb(params_list, device, results, out_sr=out_sr, out_peak=out_peak, out_lufs=out_lufs,
+               out_ceiling=out_ceiling, out_true_peak=out_true_peak, out_bits=out_bits, out_dither=out_dither,
+               out_dither_seed=out_dither_seed)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):

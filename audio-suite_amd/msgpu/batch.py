@@ -169,28 +169,13 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     """
     from .pack import PackedBatch, out_frames
 
-    if export_sr is None and export_peak is not None:
-        raise ValueError("export_peak needs export_sr")
-    if export_peak not in (None, "preset"):
-        raise ValueError("export_peak must be None or 'preset'")
-    if export_lufs is not None and export_peak is not None:
-        raise ValueError("export_lufs and export_peak are two level rules: give one")
-    if export_true_peak is not None and export_peak is not None:
-        raise ValueError("export_true_peak and export_peak are two level rules: give one")
-    if export_lufs is None and export_true_peak is None and export_ceiling is not None:
-        raise ValueError("export_ceiling needs export_lufs")
-    if export_sr is not None and devices is not None and len(list(devices)) > 1:
-        raise NotImplementedError("export_sr on more than one device (multi.py sizes its shared memory by out_n)")
-    if export_lufs is not None and devices is not None and len(list(devices)) > 1:
-        raise NotImplementedError("export_lufs on more than one device")
-    if export_true_peak is not None and devices is not None and len(list(devices)) > 1:
-        raise NotImplementedError("export_true_peak on more than one device")
+    from .export import Delivery, deliver, unpack_all
+
+    delivery = Delivery(export_sr, export_peak, export_lufs, export_ceiling, export_true_peak, export_bits,
+                        export_dither, export_dither_seed)
+    delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False)
     if export_bits is not None:
-        from .pcm import check_bits, dither_code, records, unpack, write_wav_pcm
-        check_bits(export_bits)
-        dither_code(export_dither)
-        if devices is not None and len(list(devices)) > 1:
-            raise NotImplementedError("export_bits on more than one device")
+        from .pcm import records, write_wav_pcm
     base = merged(base_params)
     pairs = variants(base, seeds, unfolds, stretches)
     keys = [key for key, _ in pairs]
@@ -223,32 +208,19 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     for chunk in _chunks(keys, lambda k: frames):
         packed = PackedBatch.variants(base, chunk)   # the template packed once (MS:1578-1584)
         out = eng.render_packed(packed)
-        offsets, lens = packed.offsets, packed.out_n
-        if export_sr is not None:                    # resampled where it lies; the copy below is the export-rate batch
-            from .dropin import resample_packed
-            peaks = [float(base["peak"])] * len(chunk) if export_peak == "preset" else None
-            out, offsets, lens = resample_packed(eng, out, offsets, lens, [base_sr] * len(chunk), out_sr, peaks)
-        if export_lufs is not None:                  # measured at the delivered rate, scaled where it lies
-            from .dropin import loudness_packed
-            loudness_packed(eng, out, offsets, lens, [out_sr] * len(chunk), export_lufs, export_ceiling,
-                            export_true_peak)
-        elif export_true_peak is not None:           # a ceiling alone
-            from .dropin import truepeak_packed
-            truepeak_packed(eng, out, offsets, lens, [out_sr] * len(chunk), export_true_peak, export_ceiling)
-        if export_bits is not None:                  # quantised last; the copy below is the byte tensor
-            from .dropin import quantize_packed
-            pcm, byte_off, nbytes, rec = quantize_packed(eng, out, offsets, lens, export_bits, export_dither,
-                                                         export_dither_seed, range(done, done + len(chunk)))
-            done += len(chunk)
-            eng.torch.cuda.synchronize(eng.device)
-            host = pcm.cpu().numpy()
-            if export_records is not None:
-                export_records.extend(records(rec))
-            for key, o, b, n in zip(chunk, byte_off, nbytes, lens):
-                emit(key, unpack(host[int(o):int(o) + int(b)], export_bits, (int(n), 2)))
-            continue
+        # resampled, levelled and quantised where it lies; the copy below is what is delivered
+        peaks = [float(base["peak"])] * len(chunk) if export_peak == "preset" else None
+        out, offsets, lens, rec = deliver(eng, out, packed.offsets, packed.out_n, [base_sr] * len(chunk), delivery,
+                                          peaks, range(done, done + len(chunk)))
+        done += len(chunk)
         eng.torch.cuda.synchronize(eng.device)
         host = out.cpu().numpy()
-        for key, off, n in zip(chunk, offsets, lens):
-            emit(key, host[off:off + n].copy())
+        if export_bits is not None:
+            if export_records is not None:
+                export_records.extend(records(rec))
+            audio = unpack_all(host, offsets, lens, export_bits)
+        else:
+            audio = [host[off:off + n].copy() for off, n in zip(offsets, lens)]
+        for key, a in zip(chunk, audio):
+            emit(key, a)
     return results

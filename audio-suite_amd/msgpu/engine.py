@@ -20,6 +20,8 @@ from .pack import PackedBatch
 DIGEST_DTYPE = np.dtype([("sum_sq", "<f8"), ("peak", "<f8"), ("sum_l", "<f8"), ("sum_r", "<f8"),
                          ("h0", "<u8"), ("h1", "<u8")])
 
+_I64P = C.POINTER(C.c_int64)
+
 
 class Engine:
     def __init__(self, device: int = 0):
@@ -149,6 +151,41 @@ class Engine:
                                     C.c_void_p(stream.cuda_stream)), self._ctx)
         return out, tuple(shape)
 
+    def _signals(self, x, offsets, lens, channels, nonneg=True, names=("x", "lens", "signal", "input")):
+        """The checks every per-signal call shares; returns (channels, offsets, lens) as the
+        library takes them.  ``nonneg=False`` leaves negative extents to the library;
+        ``names``: the caller's words for the tensor, the lengths, one signal and the tensor's role."""
+        torch = self.torch
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device.type != "cuda":
+            raise ValueError(f"{names[0]} must be a contiguous float32 device tensor")
+        channels = int(channels)
+        if channels not in (1, 2):
+            raise ValueError("channels must be 1 or 2")
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        cnt = np.ascontiguousarray(lens, dtype=np.int64)
+        if off.shape != cnt.shape or off.ndim != 1:
+            raise ValueError(f"offsets and {names[1]} must be 1-D of one length")
+        if off.size and ((nonneg and (int(off.min()) < 0 or int(cnt.min()) < 0)) or
+                         int((off + cnt).max()) * channels > x.numel()):
+            raise ValueError(f"a {names[2]} extends past the {names[3]} tensor")
+        return channels, off, cnt
+
+    def _signal_call(self, fn, x, channels, off, cnt, *args, stream=None):
+        """One per-signal entry point of the library, fn(ctx, x, [channels,] offsets, lens, n,
+        *args, stream), on ``stream`` (None: the current stream of x's device) under the
+        context's lock; ``args`` as the library takes them.  Returns the stream."""
+        if stream is None:
+            stream = self.torch.cuda.current_stream(x.device)
+        xp, op, cp = C.c_void_p(x.data_ptr()), off.ctypes.data_as(_I64P), cnt.ctypes.data_as(_I64P)
+        sp = C.c_void_p(stream.cuda_stream)
+        with self._lock:
+            if channels is None:
+                rc = fn(self._ctx, xp, op, cp, off.size, *args, sp)
+            else:
+                rc = fn(self._ctx, xp, channels, op, cp, off.size, *args, sp)
+            L.check(rc, self._ctx)
+        return stream
+
     def resample(self, x, offsets, lens, channels, up, down, h, out=None, stream=None):
         """msg_resample of signals lying in a device float32 tensor (mono samples or
         interleaved L/R frames, signal i at frame offsets[i] with lens[i] frames):
@@ -158,21 +195,10 @@ class Engine:
         out_lens), y of shape (frames,) or (frames, 2), enqueued on ``stream``."""
         from .resample import resample_len
         torch = self.torch
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.device.type != "cuda":
-            raise ValueError("x must be a contiguous float32 device tensor")
-        channels = int(channels)
-        if channels not in (1, 2):
-            raise ValueError("channels must be 1 or 2")
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
         up, down = int(up), int(down)
         if up < 1 or down < 1:
             raise ValueError("the ratio must be positive")
-        off = np.ascontiguousarray(offsets, dtype=np.int64)
-        cnt = np.ascontiguousarray(lens, dtype=np.int64)
-        if off.shape != cnt.shape or off.ndim != 1:
-            raise ValueError("offsets and lens must be 1-D of one length")
-        if off.size and (int(off.min()) < 0 or int(cnt.min()) < 0 or
-                         int((off + cnt).max()) * channels > x.numel()):
-            raise ValueError("a signal extends past the input tensor")
         out_cnt = np.array([resample_len(n, up, down) for n in cnt], dtype=np.int64)
         out_off = np.concatenate([[0], np.cumsum(out_cnt)[:-1]]).astype(np.int64) if off.size else out_cnt
         total = int(out_cnt.sum())
@@ -185,17 +211,11 @@ class Engine:
             hh = np.ascontiguousarray(h, dtype=np.float64)
             if hh.ndim != 1 or hh.size % 2 == 0:
                 raise ValueError("h must be 1-D with an odd number of taps")
-            hp, K = hh.ctypes.data_as(C.c_void_p), int(hh.size)
         else:
-            hp, K = None, 0
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        with self._lock:
-            L.check(L.lib().msg_resample(self._ctx, C.c_void_p(x.data_ptr()), channels,
-                                         off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), int(off.size), up, down, hp, K,
-                                         C.c_void_p(out.data_ptr()), out_off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                         C.c_void_p(stream.cuda_stream)), self._ctx)
+            hh = None
+        self._signal_call(L.lib().msg_resample, x, channels, off, cnt, up, down,
+                          None if hh is None else hh.ctypes.data_as(C.c_void_p), 0 if hh is None else int(hh.size),
+                          C.c_void_p(out.data_ptr()), out_off.ctypes.data_as(_I64P), stream=stream)
         return out, out_off, out_cnt
 
     def digest(self, out, offsets, out_n, stream=None):
@@ -205,42 +225,13 @@ class Engine:
         only the records (48 B each) are copied back.  Returns a numpy structured
         array with fields sum_sq, peak, sum_l, sum_r, h0, h1."""
         torch = self.torch
-        if out.dtype != torch.float32 or not out.is_contiguous() or out.device.type != "cuda":
-            raise ValueError("out must be a contiguous float32 device tensor")
-        off = np.ascontiguousarray(offsets, dtype=np.int64)
-        cnt = np.ascontiguousarray(out_n, dtype=np.int64)
-        if off.shape != cnt.shape or off.ndim != 1:
-            raise ValueError("offsets and out_n must be 1-D of one length")
-        if off.size and int((off + cnt).max()) * 2 > out.numel():
-            raise ValueError("a render extends past the output tensor")
+        _, off, cnt = self._signals(out, offsets, out_n, 2, False, ("out", "out_n", "render", "output"))
         n = int(off.size)
         rec = torch.empty((max(n, 1), 6), dtype=torch.float64, device=out.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(out.device)
-        with self._lock:
-            L.check(L.lib().msg_digest(self._ctx, C.c_void_p(out.data_ptr()),
-                                       off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                       cnt.ctypes.data_as(C.POINTER(C.c_int64)), n, C.c_void_p(rec.data_ptr()),
-                                       C.c_void_p(stream.cuda_stream)), self._ctx)
+        stream = self._signal_call(L.lib().msg_digest, out, None, off, cnt, C.c_void_p(rec.data_ptr()), stream=stream)
         with torch.cuda.stream(stream):
             host = rec.cpu().numpy()       # ordered after the digest on its stream
         return host[:n].copy().view(DIGEST_DTYPE).reshape(n)
-
-    def _signals(self, x, offsets, lens, channels):
-        torch = self.torch
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.device.type != "cuda":
-            raise ValueError("x must be a contiguous float32 device tensor")
-        channels = int(channels)
-        if channels not in (1, 2):
-            raise ValueError("channels must be 1 or 2")
-        off = np.ascontiguousarray(offsets, dtype=np.int64)
-        cnt = np.ascontiguousarray(lens, dtype=np.int64)
-        if off.shape != cnt.shape or off.ndim != 1:
-            raise ValueError("offsets and lens must be 1-D of one length")
-        if off.size and (int(off.min()) < 0 or int(cnt.min()) < 0 or
-                         int((off + cnt).max()) * channels > x.numel()):
-            raise ValueError("a signal extends past the input tensor")
-        return channels, off, cnt
 
     def loudness(self, x, offsets, lens, channels, sr, stream=None):
         """msg_loudness of signals lying in a device float32 tensor (mono samples or
@@ -249,20 +240,12 @@ class Engine:
         Returns the device records, a float64 tensor (signals, 5) whose rows are
         msg_loudness_rec (lufs, mean_sq, peak, gain, then n_blocks and n_kept as two
         int32; loudness.records reads them on the host), enqueued on ``stream``."""
-        torch = self.torch
         channels, off, cnt = self._signals(x, offsets, lens, channels)
         sr = int(sr)
         if sr < 4000 or sr % 10:
             raise ValueError("the sample rate must be a multiple of 10, at least 4000")
-        n = int(off.size)
-        rec = torch.empty((n, 5), dtype=torch.float64, device=x.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        with self._lock:
-            L.check(L.lib().msg_loudness(self._ctx, C.c_void_p(x.data_ptr()), channels,
-                                         off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), n, sr,
-                                         C.c_void_p(rec.data_ptr()), C.c_void_p(stream.cuda_stream)), self._ctx)
+        rec = self.torch.empty((int(off.size), 5), dtype=self.torch.float64, device=x.device)
+        self._signal_call(L.lib().msg_loudness, x, channels, off, cnt, sr, C.c_void_p(rec.data_ptr()), stream=stream)
         return rec
 
     def loudness_gain(self, x, offsets, lens, channels, rec, target_lufs, ceiling=None, stream=None):
@@ -278,14 +261,8 @@ class Engine:
         ceil = 0.0 if ceiling is None else float(ceiling)
         if ceiling is not None and not ceil > 0.0:
             raise ValueError("the ceiling must be positive")
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        with self._lock:
-            L.check(L.lib().msg_loudness_gain(self._ctx, C.c_void_p(x.data_ptr()), channels,
-                                              off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                              cnt.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                              C.c_void_p(rec.data_ptr()), float(target_lufs), ceil,
-                                              C.c_void_p(stream.cuda_stream)), self._ctx)
+        self._signal_call(L.lib().msg_loudness_gain, x, channels, off, cnt, C.c_void_p(rec.data_ptr()),
+                          float(target_lufs), ceil, stream=stream)
         return rec
 
     def true_peak(self, x, offsets, lens, channels, sr, stream=None):
@@ -294,20 +271,12 @@ class Engine:
         tensor (signals, 5) whose rows are msg_truepeak_rec (true_peak, peak, dbtp, gain,
         then os and a pad as two int32; truepeak.records reads them on the host),
         enqueued on ``stream``."""
-        torch = self.torch
         channels, off, cnt = self._signals(x, offsets, lens, channels)
         sr = int(sr)
         if sr < 1:
             raise ValueError("the sample rate must be positive")
-        n = int(off.size)
-        rec = torch.empty((n, 5), dtype=torch.float64, device=x.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        with self._lock:
-            L.check(L.lib().msg_truepeak(self._ctx, C.c_void_p(x.data_ptr()), channels,
-                                         off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), n, sr,
-                                         C.c_void_p(rec.data_ptr()), C.c_void_p(stream.cuda_stream)), self._ctx)
+        rec = self.torch.empty((int(off.size), 5), dtype=self.torch.float64, device=x.device)
+        self._signal_call(L.lib().msg_truepeak, x, channels, off, cnt, sr, C.c_void_p(rec.data_ptr()), stream=stream)
         return rec
 
     def true_peak_gain(self, x, offsets, lens, channels, tp_rec, loud_rec=None, target_lufs=None, ceiling_tp=None,
@@ -335,16 +304,9 @@ class Engine:
             if c is not None and not v > 0.0:
                 raise ValueError("a ceiling must be positive")
             ceil.append(v)
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        with self._lock:
-            L.check(L.lib().msg_truepeak_gain(self._ctx, C.c_void_p(x.data_ptr()), channels,
-                                              off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                              cnt.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                              None if loud_rec is None else C.c_void_p(loud_rec.data_ptr()),
-                                              C.c_void_p(tp_rec.data_ptr()),
-                                              0.0 if target_lufs is None else float(target_lufs), ceil[0], ceil[1],
-                                              C.c_void_p(stream.cuda_stream)), self._ctx)
+        self._signal_call(L.lib().msg_truepeak_gain, x, channels, off, cnt,
+                          None if loud_rec is None else C.c_void_p(loud_rec.data_ptr()), C.c_void_p(tp_rec.data_ptr()),
+                          0.0 if target_lufs is None else float(target_lufs), ceil[0], ceil[1], stream=stream)
         return tp_rec
 
     def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None):
@@ -379,16 +341,10 @@ class Engine:
               out.data_ptr() % 16):
             raise ValueError("out must be a contiguous 16-byte aligned uint8 tensor on x's device, large enough")
         rec = torch.empty((n, 4), dtype=torch.int64, device=x.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        with self._lock:
-            L.check(L.lib().msg_quantize(self._ctx, C.c_void_p(x.data_ptr()), channels,
-                                         off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), n, bits, code,
-                                         C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                         None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                         C.c_void_p(out.data_ptr()), byte_off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                         C.c_void_p(rec.data_ptr()), C.c_void_p(stream.cuda_stream)), self._ctx)
+        self._signal_call(L.lib().msg_quantize, x, channels, off, cnt, bits, code,
+                          C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                          None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(out.data_ptr()),
+                          byte_off.ctypes.data_as(_I64P), C.c_void_p(rec.data_ptr()), stream=stream)
         return out, byte_off, rec
 
     # ---- last-batch inspection -----------------------------------------

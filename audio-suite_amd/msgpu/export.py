@@ -1,0 +1,212 @@
+"""The delivery chain of a rendered batch: resample -> level -> quantise, in HBM.
+
+``render_batch`` (dropin.py, ``out_*`` options) and ``render_variations`` (batch.py,
+``export_*`` options) describe what they deliver with one ``Delivery``, check it with
+``Delivery.check`` and run it with ``deliver``; each pass works on the renders where
+they lie (resample.py, loudness.py, truepeak.py, pcm.py) and nothing here synchronises.
+A new export rule is a field of ``Delivery``, its lines in ``check`` and its step in
+``deliver``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+
+@dataclass
+class Delivery:
+    sr: object = None             # deliver at this rate (None: as rendered)
+    peak: object = None           # the peak resampled renders are rescaled to: None, "preset" or a number
+    lufs: object = None           # BS.1770 integrated loudness to deliver at
+    ceiling: object = None        # linear sample peak the levelled renders may not exceed
+    true_peak: object = None      # ceiling in dBTP
+    bits: object = None           # 16 or 24: fixed-point PCM, quantised last
+    dither: object = "tpdf"
+    dither_seed: int = 0
+
+    # the rules that work on one device only: (the rule, the option that comes with it, why)
+    _ONE_DEVICE = (("sr", "peak", " (multi.py sizes its shared memory by out_n)"), ("lufs", "ceiling", ""),
+                   ("true_peak", None, ""), ("bits", None, ""))
+
+    def one_device(self, prefix, n_devices, rules=("sr", "lufs", "true_peak", "bits"), companions=False):
+        """NotImplementedError for the first of ``rules`` asked for on more than one device;
+        ``companions``: a rule's companion option alone asks for it too (render_batch, which
+        looks at the device count before it looks at the values)."""
+        if n_devices > 1:
+            for rule, companion, why in self._ONE_DEVICE:
+                asked = getattr(self, rule) is not None or (companions and companion and
+                                                            getattr(self, companion) is not None)
+                if rule in rules and asked:
+                    raise NotImplementedError(f"{prefix}{rule} on more than one device{why}")
+
+    def check(self, prefix, results="audio", n_devices=1, numeric_peak=True):
+        """The rule table, worded with the caller's option prefix ("out_" or "export_").
+        ``results``: the result kind delivered; ``numeric_peak``: whether ``peak`` may be a
+        number (render_variations has one template preset and takes None or "preset").
+        Runs before any device call."""
+        p = prefix
+        if results not in ("audio", "stats", "device"):
+            raise ValueError("results must be 'audio', 'stats' or 'device'")
+        if self.sr is None and self.peak is not None:
+            raise ValueError(f"{p}peak needs {p}sr")
+        if not numeric_peak and self.peak not in (None, "preset"):
+            raise ValueError(f"{p}peak must be None or 'preset'")
+        for rule in ("lufs", "true_peak"):
+            if getattr(self, rule) is not None and self.peak is not None:
+                raise ValueError(f"{p}{rule} and {p}peak are two level rules: give one")
+        if self.lufs is None and self.true_peak is None and self.ceiling is not None:
+            raise ValueError(f"{p}ceiling needs {p}lufs")
+        self.one_device(p, n_devices, ("sr", "lufs", "true_peak"))
+        if self.bits is not None:
+            from .pcm import check_bits, dither_code
+            check_bits(self.bits)
+            dither_code(self.dither)
+        self.one_device(p, n_devices, ("bits",))
+        if results == "stats":
+            for rule in ("sr", "lufs", "true_peak", "bits"):
+                if getattr(self, rule) is not None:
+                    raise ValueError(f"{p}{rule} applies to results 'audio' or 'device'")
+
+
+def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
+    """Run ``delivery`` over renders lying in a device tensor ((frames, 2) float32, render i
+    at frame offsets[i] with lens[i] frames at rates[i] Hz): resampled to ``delivery.sr``
+    (``peaks``: resample_packed's), levelled at the rate delivered, quantised with the
+    dither streams (``delivery.dither_seed``, keys[i]).  Returns (tensor, offsets, lens,
+    rec): the float32 renders with frame offsets and lengths and None, or, quantised, the
+    packed bytes with byte offsets and lengths and the device PCM records.  Enqueued on
+    the current stream, no host synchronise."""
+    d = delivery
+    if d.sr is not None:
+        out, offsets, lens = resample_packed(eng, out, offsets, lens, rates, int(d.sr), peaks)
+        rates = [int(d.sr)] * len(lens)
+    _level(eng, out, offsets, lens, rates, d.lufs, d.ceiling, d.true_peak)
+    if d.bits is None:
+        return out, offsets, lens, None
+    return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys)
+
+
+def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
+    """Resample renders lying in a device output tensor ((frames, 2) float32, render i
+    at frame offsets[i] with lens[i] frames at sr_in[i] Hz) to out_sr where they lie
+    (msg_resample, one call per distinct input rate): returns (y, y_offsets, y_lens),
+    the outputs packed back to back in render order, enqueued on the current stream.
+    ``peaks`` (one per render, or None): rescale each resampled render so that
+    max|y| equals its peak, peak_normalize's rule (MS:26-29: a zero buffer stays
+    zero) -- resampling moves the peak.  Renders of one length are rescaled by one
+    reduction and one multiply over the batch."""
+    from .resample import design, ratio, resample_len
+    torch = eng.torch
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rates = [int(s) for s in sr_in]
+    ratios = [ratio(s, out_sr) for s in rates]
+    y_lens = np.array([resample_len(n, u, d) for n, (u, d) in zip(lens, ratios)], dtype=np.int64)
+    y_off = np.concatenate([[0], np.cumsum(y_lens)[:-1]]).astype(np.int64)
+    y = torch.empty((int(y_lens.sum()), 2), dtype=torch.float32, device=out.device)
+    for rate in sorted(set(rates)):
+        idx = [i for i, s in enumerate(rates) if s == rate]
+        up, down = ratio(rate, out_sr)
+        h = design(up, down) if up != down else None
+        if len(idx) == len(rates):            # one rate: the whole batch in one call
+            eng.resample(out, offsets, lens, 2, up, down, h, out=y)
+        else:                                 # mixed rates: Engine.resample packs a call's outputs back to back
+            for i in idx:
+                eng.resample(out, offsets[i:i + 1], lens[i:i + 1], 2, up, down, h, out=y[int(y_off[i]):])
+    if peaks is not None and len(y_lens):
+        pk = torch.tensor([float(p) for p in peaks], dtype=torch.float32, device=y.device)
+        if len(set(int(n) for n in y_lens)) == 1:
+            v = y.view(len(y_lens), -1)
+            m = v.abs().amax(dim=1)
+            v.mul_(torch.where(m > 0, pk / m, torch.ones_like(m)).unsqueeze(1))
+        else:
+            for i, (o, n) in enumerate(zip(y_off, y_lens)):
+                seg = y[int(o):int(o) + int(n)]
+                m = seg.abs().amax() if n else pk[i]
+                seg.mul_(torch.where(m > 0, pk[i] / m, torch.ones_like(m)))
+    return y, y_off, y_lens
+
+
+def _per_rate(eng, y, offsets, lens, rates, level):
+    """``level(offsets, lens, rate)`` over the renders of each distinct rate, in ascending
+    rate order: it measures and scales them and returns their device records (float64,
+    five columns); returns the records in render order."""
+    torch = eng.torch
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rates = [int(s) for s in rates]
+    rec = torch.empty((len(rates), 5), dtype=torch.float64, device=y.device)
+    for rate in sorted(set(rates)):
+        idx = [i for i, s in enumerate(rates) if s == rate]
+        r = level(offsets[idx], lens[idx], rate)
+        if len(idx) == len(rates):
+            return r
+        rec[torch.as_tensor(idx, device=y.device)] = r
+    return rec
+
+
+def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None, true_peak=None):
+    """Bring renders lying in a device tensor ((frames, 2) float32, render i at frame
+    offsets[i] with lens[i] frames at rates[i] Hz) to ``target_lufs`` where they lie:
+    msg_loudness then msg_loudness_gain per distinct rate, the gain formed on the
+    device from each render's record (no host synchronise).  ``ceiling``: a linear
+    sample peak no render may exceed (None: no limit).  ``true_peak``: a ceiling in
+    dBTP (BS.1770 true peak, truepeak.py) no render may exceed: msg_truepeak is
+    measured too and msg_truepeak_gain forms the one gain from both records.  Scales y
+    in place and returns the device records in render order (engine.Engine.loudness)."""
+    def level(off, cnt, rate):
+        r = eng.loudness(y, off, cnt, 2, rate)
+        if true_peak is None:
+            eng.loudness_gain(y, off, cnt, 2, r, float(target_lufs), ceiling)
+        else:
+            t = eng.true_peak(y, off, cnt, 2, rate)
+            eng.true_peak_gain(y, off, cnt, 2, t, r, float(target_lufs), _dbtp(true_peak), ceiling)
+        return r
+    return _per_rate(eng, y, offsets, lens, rates, level)
+
+
+def _dbtp(true_peak):
+    """A dBTP ceiling as a linear true peak."""
+    v = float(true_peak)
+    if not np.isfinite(v):
+        raise ValueError("the true-peak ceiling must be a number of dBTP")
+    return 10.0 ** (v / 20.0)
+
+
+def truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling=None):
+    """Hold renders lying in a device tensor (as loudness_packed) under ``true_peak`` dBTP
+    where they lie, with no loudness target: msg_truepeak then msg_truepeak_gain per
+    distinct rate, the gain (1 where the ceiling does not bind) formed on the device.
+    ``ceiling``: a linear sample peak as well (None: no limit).  Scales y in place and
+    returns the device records in render order (engine.Engine.true_peak)."""
+    def level(off, cnt, rate):
+        t = eng.true_peak(y, off, cnt, 2, rate)
+        eng.true_peak_gain(y, off, cnt, 2, t, None, None, _dbtp(true_peak), ceiling)
+        return t
+    return _per_rate(eng, y, offsets, lens, rates, level)
+
+
+def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak):
+    if lufs is not None:
+        loudness_packed(eng, y, offsets, lens, rates, lufs, ceiling, true_peak)
+    elif true_peak is not None:
+        truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling)
+
+
+def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=None):
+    """Renders lying in a device tensor (as loudness_packed) as ``bits``-bit PCM, quantised
+    and packed on the device after every level rule (msg_quantize, pcm.py): render i
+    takes its dither from the stream (seed, keys[i]).  Returns the device byte tensor,
+    each render's byte offset and length in it, and the device records (no host synchronise)."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    out, byte_off, rec = eng.quantize(y, offsets, lens, 2, bits, dither, seed, keys)
+    return out, byte_off, lens * (2 * (int(bits) // 8)), rec
+
+
+def unpack_all(host, byte_off, nbytes, bits):
+    """The integer arrays (frames, 2) of quantize_packed's bytes once they are on the host."""
+    from .pcm import unpack
+    frame = 2 * (int(bits) // 8)
+    return [unpack(host[int(o):int(o) + int(b)], bits, (int(b) // frame, 2)) for o, b in zip(byte_off, nbytes)]

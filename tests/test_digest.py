@@ -177,6 +177,13 @@ def test_device_digest_equals_host(irs, golden_info):
             continue
         assert abs(s["rms"] - ref["rms"]) <= 1e-5
         assert abs(s["sum_l"] - ref["sum_l"]) <= 1e-5 * s["out_n"]
+    # renders without a tile among the others: they share their successor's first tile
+    lens = [0, 1, 2048, 0, 2049, 0]
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    a = (np.random.default_rng(9).standard_normal((sum(lens), 2)) * 0.4).astype(np.float32)
+    rz = eng.digest(torch.from_numpy(a).cuda(), offs, lens)
+    for i, (o, n) in enumerate(zip(offs, lens)):
+        assert as_dict(rz[i]) == as_dict(multi.digest_host(a[o:o + n])), (i, n)
     # a C5-length render: 4097 tiles, several per thread in the preset fold
     p5 = msgpu.config_params("C5", seed=1000, irs=irs)
     pk = PackedBatch([p5])

@@ -70,7 +70,8 @@ def check_against_host(host_bytes, byte_off, recs, signals, channels, bits, mode
 @pytest.mark.parametrize("bits", PC.BITS)
 @pytest.mark.parametrize("channels", [1, 2])
 def test_device_equals_host(eng, channels, bits, mode):
-    sig = PC.signals(channels)
+    tile = 4096 // channels                                 # frames of one tile; empty signals between, last too
+    sig = PC.signals(channels) + [PC.signal(n * channels, channels, 0.3) for n in (0, 1, tile, 0, tile + 1, 0)]
     keys = [1000 + 7 * i for i in range(len(sig))]
     host_bytes, byte_off, recs = device_quantize(eng, sig, channels, bits, mode, keys)
     check_against_host(host_bytes, byte_off, recs, sig, channels, bits, mode, keys)

@@ -124,9 +124,17 @@ def test_impulses(eng, up, down, channels):
 @pytest.mark.parametrize("channels", [1, 2])
 @pytest.mark.parametrize("up,down", [(1, 8), (147, 160)])
 def test_ragged_batch(eng, up, down, channels):
-    torch = eng.torch
     h = design(up, down)
-    lens = [1, 4097, 30001, 8, 12345]
+    ragged_batch(eng, up, down, channels, h, [1, 4097, 30001, 8, 12345])
+    # signals without a tile share their successor's first tile: outputs of 0, 1, tile, 0, tile + 1, 0 frames
+    tile = tile_frames(up, down, h.size, channels)
+    lens = [0, 1, tile * down // up, 0, (tile + 1) * down // up, 0]
+    assert [resample_len(n, up, down) for n in lens] == [0, 1, tile, 0, tile + 1, 0]
+    ragged_batch(eng, up, down, channels, h, lens)
+
+
+def ragged_batch(eng, up, down, channels, h, lens):
+    torch = eng.torch
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]])        # back to back: mono rows start at odd floats
     rng = np.random.default_rng(5)
     x = rng.standard_normal((sum(lens), 2) if channels == 2 else sum(lens)).astype(np.float32)
@@ -137,7 +145,7 @@ def test_ragged_batch(eng, up, down, channels):
                      dtype=torch.float32, device="cuda")
     y, yo, yn = eng.resample(xd, offs, lens, channels, up, down, h, out=out)
     assert y is out
-    alone = [eng.resample(xd[o:o + n].clone(), [0], [n], channels, up, down, h)[0].cpu().numpy()
+    alone = [eng.resample(xd[o:o + n].clone(), [0], [n], channels, up, down, h)[0].cpu().numpy() if n else x[:0]
              for o, n in zip(offs, lens)]
     torch.cuda.synchronize()
     y = y.cpu().numpy()
@@ -146,6 +154,8 @@ def test_ragged_batch(eng, up, down, channels):
     for i, (o, n) in enumerate(zip(offs, lens)):
         got = y[yo[i]:yo[i] + yn[i]]
         assert got.shape == alone[i].shape and np.array_equal(got, alone[i])
+        if n == 0:
+            continue
         want = reference(x[o:o + n], up, down, h)
         for c in range(channels):
             err = rel_rms(got[:, c] if channels == 2 else got, want[:, c] if channels == 2 else want)
