@@ -33,7 +33,7 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "msgpu", "libmsgpu.so")
 TUS = ["msgpu.hip", "k_spectral.hip", "k_spectral_ct.hip", "k_spec3.hip", "k_fir.hip", "k_grain64.hip", "k_grain64_lds.hip",
        "k_grain64_glb.hip", "k_stereo_odd.hip", "k_fir64.hip", "k_stereo.hip", "k_digest.hip", "k_resample.hip",
-       "k_loudness.hip", "k_truepeak.hip", "k_pcm.hip"]
+       "k_loudness.hip", "k_truepeak.hip", "k_pcm.hip", "k_limit.hip"]
 HEADERS = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
           [os.path.join(os.path.dirname(HERE), "include", "msgpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -49,7 +49,10 @@ TU_HOST_FLAGS = {"msgpu.hip": ["-Xarch_host", "-msse4.1"],
                  # (27 VALU instructions per 16 FMAs against 20), so it is off for this TU
                  "k_resample.hip": ["-fno-slp-vectorize"],
                  # the true-peak interpolator slides the same kind of window (kernels_truepeak.h)
-                 "k_truepeak.hip": ["-fno-slp-vectorize"]}
+                 "k_truepeak.hip": ["-fno-slp-vectorize"],
+                 # the limiter's envelope is that window again, and its FIR slides two 16-byte reads
+                 # and its demand c / e must be the correctly rounded divide (limit.h): the default, spelled out
+                 "k_limit.hip": ["-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 
 
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)

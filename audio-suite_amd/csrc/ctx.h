@@ -374,6 +374,14 @@ struct msg_ctx {
     // msg_quantize: signal extents, tile bases, stream keys and output offsets; per-tile partials
     DevBuf<int64_t> pcm_meta;
     DevBuf<int4> pcm_part;
+    // msg_limit: signal extents, both kernels' tile bases and the scratch offsets; the smoothing
+    // weights; r of every frame; per envelope tile the NaN flag; per signal the state; per apply
+    // tile the least gain and the count
+    DevBuf<int64_t> lim_meta;
+    DevBuf<float> lim_w, lim_r;
+    DevBuf<uint32_t> lim_nan;
+    DevBuf<int32_t> lim_state;
+    DevBuf<uint2> lim_part;
 
     // What must come first and in this order; the members' destructors follow.
     ~msg_ctx() {

@@ -1,11 +1,13 @@
 // host_abi.inc — the host-side entry points of the C ABI (include/msgpu.h): the record
 // sizes (msg_sizeof), the render plan (plan.h), the NumPy stream primitives (nprng.h) and
 // the host references of the render digest (digest.h), of the loudness and true-peak
-// measurements (loudness.h, truepeak.h) and of the PCM quantiser (pcm.h).  Included
+// measurements (loudness.h, truepeak.h), of the PCM quantiser (pcm.h) and of the look-ahead
+// limiter (limit.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
-// named above (DigestPart / dg_host, LoudRec / ld_host, TruePeakRec / tp_host, PcmRec / pcm_host).
+// named above (DigestPart / dg_host, LoudRec / ld_host, TruePeakRec / tp_host, PcmRec / pcm_host,
+// LimitRec / lim_host).
 
 int64_t msg_sizeof(int32_t which) {
     switch (which) {
@@ -16,6 +18,7 @@ int64_t msg_sizeof(int32_t which) {
         case 4: return (int64_t)sizeof(msg_loudness_rec);
         case 5: return (int64_t)sizeof(msg_truepeak_rec);
         case 6: return (int64_t)sizeof(msg_pcm_rec);
+        case 7: return (int64_t)sizeof(msg_limit_rec);
         default: return -1;
     }
 }
@@ -154,6 +157,30 @@ int msg_quantize_host(const float* x, int32_t channels, int64_t n, int32_t bits,
     if (!pcm_dither_ok(dither)) return fail(nullptr, MSG_E_VALUE, "dither must be MSG_DITHER_NONE or MSG_DITHER_TPDF");
     PcmRec r;
     pcm_host(x, channels, n, bits, dither, seed, key, out, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The value checks msg_limit and msg_limit_host share, in their order
+static int lim_values(msg_ctx* ctx, int32_t sr, double ceiling_tp, int32_t lookahead_frames) {
+    if (sr < 1) return fail(ctx, MSG_E_VALUE, "the sample rate must be positive");
+    if (!(ceiling_tp > 0.0) || !std::isfinite(ceiling_tp) || !((float)ceiling_tp > 0.0f) || !std::isfinite((float)ceiling_tp))
+        return fail(ctx, MSG_E_VALUE, "the ceiling must be a finite positive number");
+    if (lookahead_frames < 1) return fail(ctx, MSG_E_VALUE, "the look-ahead must be at least one frame");
+    if (lookahead_frames > LIM_L_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "look-ahead beyond 4096 frames");
+    return MSG_OK;
+}
+
+// The look-ahead limiter over one signal in host memory, in place: the definition of
+// limit.h as one loop (lim_host), the device's samples and record to the bit
+int msg_limit_host(float* x, int32_t channels, int64_t n, int32_t sr, double ceiling_tp, int32_t lookahead_frames,
+                   msg_limit_rec* rec) {
+    static_assert(sizeof(LimitRec) == sizeof(msg_limit_rec), "LimitRec is msg_limit_rec");
+    if (!rec || n < 0 || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    if (const int rc = lim_values(nullptr, sr, ceiling_tp, lookahead_frames)) return rc;
+    LimitRec r;
+    lim_host(x, channels, n, sr, (float)ceiling_tp, lookahead_frames, &r);
     std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }

@@ -3,7 +3,8 @@
 // (plan.h, msg_plan_host), the NumPy stream primitives (nprng.h, msg_rng_*) and
 // the host references of the render digest (digest.h, msg_digest_host) and of the
 // loudness and true-peak measurements (loudness.h, msg_loudness_host; truepeak.h,
-// msg_truepeak_host) and of the PCM quantiser (pcm.h, msg_quantize_host),
+// msg_truepeak_host), of the PCM quantiser (pcm.h, msg_quantize_host) and of the
+// look-ahead limiter (limit.h, msg_limit_host),
 // compiled by g++ with -fsanitize=address,undefined into
 // msgpu/libmsgpu_hostsan.so.  The device entry points are stubs that fail with
 // MSG_E_DEVICE, so the ctypes binding (_lib.py) loads this library unchanged
@@ -24,6 +25,7 @@
 #include "loudness.h"
 #include "truepeak.h"
 #include "pcm.h"
+#include "limit.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -90,6 +92,10 @@ int msg_truepeak_gain(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*,
 }
 int msg_quantize(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, uint64_t,
                  const uint64_t*, void*, const int64_t*, msg_pcm_rec*, void*) {
+    return no_device();
+}
+int msg_limit(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, double, int32_t,
+              const msg_truepeak_rec*, msg_limit_rec*, void*) {
     return no_device();
 }
 #include "host_abi.inc"

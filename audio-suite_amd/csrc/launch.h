@@ -211,3 +211,14 @@ hipError_t launch_truepeak_gain(int n_sig, int channels, unsigned tiles, hipStre
 // (pcm_tiles of the words), stream keys, output byte offsets; part: one int4 per tile
 hipError_t launch_pcm(int n_sig, int channels, int bits, int dither, unsigned tiles, hipStream_t s, const float* x,
                       const int64_t* meta, void* out, void* part, void* rec);
+
+// look-ahead true-peak limiter (kernels_limit.h): the envelope over env_tiles tiles of LIM_ENV_TILE
+// frames into rbuf and nanpart, one wave per signal into state, the apply over tiles of
+// lim_tile(L) frames in place, then one wave per signal into rec (msg_limit_rec records).
+// meta: offsets, frames, n_sig + 1 first apply tiles, n_sig first scratch floats, n_sig + 1
+// first envelope tiles; tab: tp_table; w: lim_weights(L); tp_rec: measured records or null;
+// part: one uint2 per apply tile
+void limit_init_attrs();
+hipError_t launch_limit(int n_sig, int channels, int os, unsigned env_tiles, unsigned tiles, hipStream_t s, float* x,
+                        const int64_t* meta, const float* tab, float c32, int L, const float* w, const void* tp_rec,
+                        float* rbuf, uint32_t* nanpart, int32_t* state, void* part, void* rec);

@@ -36,6 +36,7 @@
 #include "loudness.h"
 #include "truepeak.h"
 #include "pcm.h"
+#include "limit.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"
@@ -462,6 +463,7 @@ msg_ctx* msg_create(int device_ordinal) {
     grain64_init_attrs();
     stereo_odd_init_attrs();
     fir64_init_attrs();
+    limit_init_attrs();
     return ctx.release();
 }
 

@@ -1,6 +1,6 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
-// msg_loudness, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize.
+// msg_loudness, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_limit.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -261,5 +261,44 @@ int msg_quantize(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64
     HIPCHK(ctx, ctx->pcm_part.ensure(c.parts()));
     HIPCHK(ctx, launch_pcm(n_signals, channels, bits, dither, (unsigned)c.tiles, c.s, x_dev, ctx->pcm_meta.p, out_dev,
                            ctx->pcm_part.p, rec_dev));
+    return c.finish();
+}
+
+int msg_limit(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n, int32_t n_signals,
+              int32_t sr, double ceiling_tp, int32_t lookahead_frames, const msg_truepeak_rec* tp_rec_dev,
+              msg_limit_rec* rec_dev, void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && rec_dev, n_signals, channels)) return rc;
+    if (const int rc = lim_values(ctx, sr, ceiling_tp, lookahead_frames)) return rc;
+    if (const int rc = sig_aligned(ctx, channels, x_dev)) return rc;
+    if (n_signals == 0) return MSG_OK;
+    const int L = lookahead_frames;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, [L](int64_t f) { return lim_tiles(f, L); }, "signal", "limiter",
+                              (size_t)2 * n_signals + 1))
+        return rc;
+    if (c.tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    // each signal's r in the scratch from a multiple of four floats, and the envelope's own tiles
+    int64_t* r_row = c.extra_row(n_signals, 0);
+    int64_t* env_row = c.extra_row(n_signals, 1);
+    int64_t r_floats = 0, env_tiles = 0;
+    for (int i = 0; i < n_signals; ++i) {
+        r_row[i] = r_floats;
+        env_row[i] = env_tiles;
+        r_floats += (n[i] + 3) / 4 * 4;
+        env_tiles += lim_env_tiles(n[i]);
+    }
+    env_row[n_signals] = env_tiles;
+    if (env_tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many limiter tiles");
+    std::vector<float> w((size_t)lim_taps4(L));
+    lim_weights(L, w.data());
+    if (const int rc = c.open(ctx->lim_meta)) return rc;
+    HIPCHK(ctx, ctx->lim_r.ensure((size_t)r_floats + 4));
+    HIPCHK(ctx, ctx->lim_nan.ensure((size_t)std::max<int64_t>(1, env_tiles)));
+    HIPCHK(ctx, ctx->lim_state.ensure((size_t)n_signals));
+    HIPCHK(ctx, ctx->lim_part.ensure(c.parts()));
+    if (const int rc = c.upload(ctx->lim_w, w)) return rc;
+    HIPCHK(ctx, launch_limit(n_signals, channels, tp_os(sr), (unsigned)env_tiles, (unsigned)c.tiles, c.s, x_dev,
+                             ctx->lim_meta.p, ctx->d_tp_tab.p, (float)ceiling_tp, L, ctx->lim_w.p, tp_rec_dev,
+                             ctx->lim_r.p, ctx->lim_nan.p, ctx->lim_state.p, ctx->lim_part.p, rec_dev));
     return c.finish();
 }

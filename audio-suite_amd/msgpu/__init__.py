@@ -16,6 +16,7 @@ from . import resample as _resample  # noqa: F401
 from . import loudness as _loudness  # noqa: F401  (the same for ``msgpu.loudness``)
 from . import truepeak as _truepeak  # noqa: F401
 from . import pcm as _pcm  # noqa: F401
+from . import limit as _limit  # noqa: F401
 
 
 def render(params, progress=None, device: int = 0):
@@ -25,7 +26,7 @@ def render(params, progress=None, device: int = 0):
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
                  out_lufs=None, out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf",
-                 out_dither_seed=0):
+                 out_dither_seed=0, out_limiter=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -42,10 +43,12 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     ``out_bits``: 16 or 24, deliver fixed-point PCM quantised on the device after every
     other rule (pcm.py; one device only): "audio" gives int16 / int32 arrays, "device"
     views of the packed byte tensor; ``out_dither`` "tpdf" or "none", from the stream
-    (``out_dither_seed``, the preset's index in ``params_list``)."""
+    (``out_dither_seed``, the preset's index in ``params_list``).  ``out_limiter``: hold
+    ``out_true_peak`` with the look-ahead true-peak limiter (limit.py; one device only)
+    instead of one static gain: None off, True a 5 ms look-ahead, a number of milliseconds."""
     if devices is not None and len(list(devices)) > 1:
         from .export import Delivery
-        Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits).one_device(
+        Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, limiter=out_limiter).one_device(
             "out_", len(list(devices)), companions=True)
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)
@@ -54,7 +57,7 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     from .dropin import render_batch as _rb
     return _rb(params_list, device, results, out_sr=out_sr, out_peak=out_peak, out_lufs=out_lufs,
                out_ceiling=out_ceiling, out_true_peak=out_true_peak, out_bits=out_bits, out_dither=out_dither,
-               out_dither_seed=out_dither_seed)
+               out_dither_seed=out_dither_seed, out_limiter=out_limiter)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):
@@ -104,6 +107,14 @@ def true_peak(x, sr, device: int = 0, db: bool = False):
     return _truepeak.true_peak(x, sr, device, db)
 
 
+def limit(x, sr, ceiling_dbtp=-1.0, lookahead_ms=5.0, device: int = 0):
+    """Hold x, (n,) or (n, 2), at sr Hz under ``ceiling_dbtp`` dBTP with the look-ahead
+    true-peak limiter on the device (see limit.py).  NumPy in: a limited float32 copy and
+    its record out; a device tensor in: limited in place with no host synchronise, the
+    device record tensor out."""
+    return _limit.limit(x, sr, ceiling_dbtp, lookahead_ms, device)
+
+
 def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0):
     """x, (n,) or (n, 2) float32, as 16- or 24-bit PCM quantised on the device with TPDF
     dither (or "none") from the stream (seed, key); see pcm.py.  NumPy in, int16 (or
@@ -117,6 +128,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     shards the variants across GPUs as render_batch does; ``export_sr`` /
     ``export_peak`` deliver the variants at another sample rate, ``export_lufs`` /
     ``export_ceiling`` at a BS.1770 integrated loudness, ``export_true_peak`` under a
-    ceiling in dBTP, ``export_bits`` as 16- or 24-bit PCM with TPDF dither (one device)."""
+    ceiling in dBTP, ``export_bits`` as 16- or 24-bit PCM with TPDF dither, ``export_limiter`` holding
+    that ceiling with the look-ahead limiter (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

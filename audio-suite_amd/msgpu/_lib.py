@@ -100,6 +100,11 @@ class MsgPcmRec(C.Structure):
                 ("bits", C.c_int32), ("dither", C.c_int32)]
 
 
+class MsgLimitRec(C.Structure):
+    _fields_ = [("min_gain", C.c_double), ("reduction_db", C.c_double), ("limited_frames", C.c_int64),
+                ("lookahead", C.c_int32), ("state", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -154,6 +159,9 @@ _PROTOS = {
                                C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "msg_quantize_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
                                     C.c_void_p, C.c_void_p]),
+    "msg_limit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                            C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "msg_limit_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_void_p]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
@@ -191,7 +199,7 @@ def lib() -> C.CDLL:
             if L.msg_abi_version() != ABI_VERSION:
                 raise RuntimeError("libmsgpu ABI version mismatch")
             for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec, MsgLoudnessRec,
-                                        MsgTruePeakRec, MsgPcmRec)):
+                                        MsgTruePeakRec, MsgPcmRec, MsgLimitRec)):
                 if L.msg_sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmsgpu struct {st.__name__} size mismatch: "
                                        f"{L.msg_sizeof(which)} != {C.sizeof(st)}")

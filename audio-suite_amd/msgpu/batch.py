@@ -131,7 +131,7 @@ def _chunks(items, frames_of):
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0,
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
                       export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
-                      export_dither="tpdf", export_dither_seed=0, export_records=None):
+                      export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -166,13 +166,20 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     names, and the returned audio is the integer array in the file (int16, or int32 at
     24 bits).  ``export_records``: a list that gets every variant's msg_pcm_rec
     (pcm.PCM_DTYPE: clipped, nan, q_min, q_max, bits, dither) appended.  One device only.
+
+    ``export_limiter``: hold ``export_true_peak`` with the look-ahead true-peak limiter
+    (limit.py) instead of one static gain: only the frames around a peak over the ceiling
+    are turned down, so a variant with a stray peak is delivered at ``export_lufs`` and not
+    below it by that peak's excess.  None off, True a 5 ms look-ahead, a positive number
+    that many milliseconds; a static trim after it holds the ceiling on dense material.
+    Needs ``export_true_peak``.  One device only.
     """
     from .pack import PackedBatch, out_frames
 
     from .export import Delivery, deliver, unpack_all
 
     delivery = Delivery(export_sr, export_peak, export_lufs, export_ceiling, export_true_peak, export_bits,
-                        export_dither, export_dither_seed)
+                        export_dither, export_dither_seed, export_limiter)
     delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False)
     if export_bits is not None:
         from .pcm import records, write_wav_pcm

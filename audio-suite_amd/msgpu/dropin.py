@@ -26,7 +26,7 @@ import numpy as np
 
 from .engine import default_engine
 from .export import (Delivery, deliver, unpack_all,  # noqa: F401  (the packed passes stay importable from here)
-                     loudness_packed, quantize_packed, resample_packed, truepeak_packed)
+                     limiter_packed, loudness_packed, quantize_packed, resample_packed, truepeak_packed)
 from .pack import PackedBatch, design_sr
 from .params import first_missing_key, merged
 
@@ -93,7 +93,8 @@ def _out_peaks(params_list, out_peak):
 
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
-                 out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0):
+                 out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
+                 out_limiter=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -107,8 +108,12 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     (truepeak_packed, loudness_packed).  ``out_bits``: 16 or 24, deliver fixed-point PCM,
     quantised last on the device (quantize_packed) with ``out_dither`` ("tpdf" or "none")
     from the stream (``out_dither_seed``, the preset's index): int16 / int32 arrays
-    ("audio") or views of the packed byte tensor ("device")."""
-    delivery = Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, out_dither, out_dither_seed)
+    ("audio") or views of the packed byte tensor ("device").  ``out_limiter``: hold
+    ``out_true_peak`` with the look-ahead limiter (export.limiter_packed) instead of one
+    static gain, so a render with a stray peak keeps its loudness: None off, True a 5 ms
+    look-ahead, a positive number that many milliseconds."""
+    delivery = Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, out_dither, out_dither_seed,
+                        out_limiter)
     delivery.check("out_", results)
     params_list = list(params_list)
     eng = default_engine(device)

@@ -309,6 +309,29 @@ class Engine:
                           0.0 if target_lufs is None else float(target_lufs), ceil[0], ceil[1], stream=stream)
         return tp_rec
 
+    def limit(self, x, offsets, lens, channels, sr, ceiling_tp, lookahead_frames, tp_rec=None, stream=None):
+        """msg_limit: the look-ahead true-peak limiter over signals lying in a device float32
+        tensor (as Engine.true_peak), in place: each is held under ``ceiling_tp``, a linear
+        true peak, with a look-ahead of ``lookahead_frames`` (limit.py).  ``tp_rec``: the
+        signals' device records of Engine.true_peak measured on these samples; a signal
+        measured under the ceiling is then skipped on the device.  Returns the device
+        records, a float64 tensor (signals, 4) whose rows are msg_limit_rec (limit.records
+        reads them on the host); enqueued on ``stream``, no host synchronise."""
+        torch = self.torch
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        sr, la, c = int(sr), int(lookahead_frames), float(ceiling_tp)
+        if sr < 1:
+            raise ValueError("the sample rate must be positive")
+        n = int(off.size)
+        if tp_rec is not None and (tp_rec.dtype != torch.float64 or not tp_rec.is_contiguous() or
+                                   tp_rec.device != x.device or tp_rec.numel() < 5 * n):
+            raise ValueError("tp_rec must be the float64 record tensor of Engine.true_peak on x's device")
+        rec = torch.empty((n, 4), dtype=torch.float64, device=x.device)
+        self._signal_call(L.lib().msg_limit, x, channels, off, cnt, sr, c, la,
+                          None if tp_rec is None else C.c_void_p(tp_rec.data_ptr()), C.c_void_p(rec.data_ptr()),
+                          stream=stream)
+        return rec
+
     def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None):
         """msg_quantize of signals lying in a device float32 tensor (as Engine.true_peak):
         ``bits``-bit PCM (16 or 24) with ``dither`` ("tpdf" or "none") from the stream

@@ -3,7 +3,7 @@
 ``render_batch`` (dropin.py, ``out_*`` options) and ``render_variations`` (batch.py,
 ``export_*`` options) describe what they deliver with one ``Delivery``, check it with
 ``Delivery.check`` and run it with ``deliver``; each pass works on the renders where
-they lie (resample.py, loudness.py, truepeak.py, pcm.py) and nothing here synchronises.
+they lie (resample.py, loudness.py, truepeak.py, limit.py, pcm.py) and nothing here synchronises.
 A new export rule is a field of ``Delivery``, its lines in ``check`` and its step in
 ``deliver``.
 """
@@ -24,12 +24,26 @@ class Delivery:
     bits: object = None           # 16 or 24: fixed-point PCM, quantised last
     dither: object = "tpdf"
     dither_seed: int = 0
+    limiter: object = None        # hold true_peak with the look-ahead limiter: None off, True 5 ms, a number of ms
 
     # the rules that work on one device only: (the rule, the option that comes with it, why)
     _ONE_DEVICE = (("sr", "peak", " (multi.py sizes its shared memory by out_n)"), ("lufs", "ceiling", ""),
-                   ("true_peak", None, ""), ("bits", None, ""))
+                   ("true_peak", None, ""), ("bits", None, ""), ("limiter", None, ""))
 
-    def one_device(self, prefix, n_devices, rules=("sr", "lufs", "true_peak", "bits"), companions=False):
+    def limiter_ms(self):
+        """The limiter's look-ahead in milliseconds, None when it is off; ValueError for
+        anything but None, True or a finite positive number."""
+        v = self.limiter
+        if v is None:
+            return None
+        if v is True:
+            return 5.0
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(float(v)) or not float(v) > 0.0:
+            raise ValueError("the limiter is None, True or a positive number of milliseconds")
+        return float(v)
+
+    def one_device(self, prefix, n_devices, rules=("sr", "lufs", "true_peak", "bits", "limiter"), companions=False):
         """NotImplementedError for the first of ``rules`` asked for on more than one device;
         ``companions``: a rule's companion option alone asks for it too (render_batch, which
         looks at the device count before it looks at the values)."""
@@ -63,8 +77,16 @@ class Delivery:
             check_bits(self.bits)
             dither_code(self.dither)
         self.one_device(p, n_devices, ("bits",))
+        if self.limiter is not None:
+            try:
+                self.limiter_ms()
+            except ValueError:
+                raise ValueError(f"{p}limiter must be None, True or a positive number of milliseconds") from None
+            if self.true_peak is None:
+                raise ValueError(f"{p}limiter needs {p}true_peak")
+        self.one_device(p, n_devices, ("limiter",))
         if results == "stats":
-            for rule in ("sr", "lufs", "true_peak", "bits"):
+            for rule in ("sr", "lufs", "true_peak", "bits", "limiter"):
                 if getattr(self, rule) is not None:
                     raise ValueError(f"{p}{rule} applies to results 'audio' or 'device'")
 
@@ -81,7 +103,7 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     if d.sr is not None:
         out, offsets, lens = resample_packed(eng, out, offsets, lens, rates, int(d.sr), peaks)
         rates = [int(d.sr)] * len(lens)
-    _level(eng, out, offsets, lens, rates, d.lufs, d.ceiling, d.true_peak)
+    _level(eng, out, offsets, lens, rates, d.lufs, d.ceiling, d.true_peak, d.limiter_ms())
     if d.bits is None:
         return out, offsets, lens, None
     return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys)
@@ -187,8 +209,42 @@ def truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling=None):
     return _per_rate(eng, y, offsets, lens, rates, level)
 
 
-def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak):
-    if lufs is not None:
+def limiter_packed(eng, y, offsets, lens, rates, true_peak, lookahead_ms, lufs=None, ceiling=None):
+    """Hold renders lying in a device tensor (as loudness_packed) under ``true_peak`` dBTP with
+    the look-ahead limiter instead of one static gain, per distinct rate: levelled to
+    ``lufs`` first when given (msg_loudness, msg_loudness_gain with no ceiling), then
+    msg_truepeak and msg_limit (a render measured under the ceiling is skipped on the
+    device), then msg_truepeak again and msg_truepeak_gain as a static trim, which is 1
+    wherever the limiter was enough and also holds ``ceiling``, the linear sample peak.
+    Works in place and returns the limiter's device records in render order
+    (engine.Engine.limit); no host synchronise."""
+    from .limit import lookahead_frames
+    torch = eng.torch
+    c = _dbtp(true_peak)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rates = [int(s) for s in rates]
+    rec = torch.empty((len(rates), 4), dtype=torch.float64, device=y.device)
+    for rate in sorted(set(rates)):
+        idx = [i for i, s in enumerate(rates) if s == rate]
+        off, cnt = offsets[idx], lens[idx]
+        if lufs is not None:
+            r = eng.loudness(y, off, cnt, 2, rate)
+            eng.loudness_gain(y, off, cnt, 2, r, float(lufs), None)
+        t = eng.true_peak(y, off, cnt, 2, rate)
+        lim = eng.limit(y, off, cnt, 2, rate, c, lookahead_frames(rate, lookahead_ms), tp_rec=t)
+        t2 = eng.true_peak(y, off, cnt, 2, rate)
+        eng.true_peak_gain(y, off, cnt, 2, t2, None, None, c, ceiling)
+        if len(idx) == len(rates):
+            return lim
+        rec[torch.as_tensor(idx, device=y.device)] = lim
+    return rec
+
+
+def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak, limiter_ms=None):
+    if limiter_ms is not None:
+        limiter_packed(eng, y, offsets, lens, rates, true_peak, limiter_ms, lufs, ceiling)
+    elif lufs is not None:
         loudness_packed(eng, y, offsets, lens, rates, lufs, ceiling, true_peak)
     elif true_peak is not None:
         truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling)

@@ -17,6 +17,7 @@
  *   msg_loudness     BS.1770 integrated loudness and LUFS gain in HBM (no counterpart)
  *   msg_truepeak     BS.1770 true peak and a dBTP ceiling in HBM   (no counterpart)
  *   msg_quantize     16/24-bit PCM with TPDF dither, packed in HBM  (sf.write's subtype, MS:1589)
+ *   msg_limit        look-ahead true-peak limiter in HBM            (no counterpart)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
 #ifndef MSGPU_H
@@ -118,7 +119,7 @@ int         msg_abi_version(void);
  * MSGPU_HOST_THREADS, else the CPU affinity / LOCAL_WORLD_SIZE, at most 16. */
 int         msg_host_threads(void);
 /* sizeof of the ABI structs (0 msg_preset, 1 msg_event, 2 msg_plan_info, 3 msg_digest_rec,
- * 4 msg_loudness_rec, 5 msg_truepeak_rec, 6 msg_pcm_rec) for binding checks */
+ * 4 msg_loudness_rec, 5 msg_truepeak_rec, 6 msg_pcm_rec, 7 msg_limit_rec) for binding checks */
 int64_t     msg_sizeof(int32_t which);
 msg_ctx*    msg_create(int device_ordinal);
 void        msg_destroy(msg_ctx* ctx);
@@ -384,6 +385,41 @@ int msg_quantize(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64
  * `channels` interleaved words; out: n channels bits / 8 bytes); needs no device. */
 int msg_quantize_host(const float* x, int32_t channels, int64_t n, int32_t bits, int32_t dither, uint64_t seed,
                       uint64_t key, void* out, msg_pcm_rec* rec);
+
+/* Look-ahead true-peak limiter of signals lying in HBM, in place (csrc/limit.h holds the
+ * definition, DESIGN.md 4f the kernels).  Per frame: the envelope e, the larger of the
+ * sample and of the oversampled values on both sides of it (msg_truepeak's interpolator),
+ * over the channels; the demand r = min(1, c / e) with c = (float)ceiling_tp, linear; its
+ * minimum over +-(lookahead_frames + 12) frames; that smoothed by a Hann window of
+ * 2 lookahead_frames + 1 unit-sum weights; g the smaller of the result and r.  Frames
+ * farther than 2 lookahead_frames + 12 from every frame with e > c keep their bits.  All in
+ * float32 in one fixed order: host and device agree to the bit, samples and records.
+ *   min_gain        the least g (1 if nothing was limited)
+ *   reduction_db    -20 log10(min_gain), correctly rounded
+ *   limited_frames  frames with g < 1
+ *   lookahead       lookahead_frames
+ *   state           0 untouched, 1 limited, 2 a NaN in the signal: left as it was
+ * The sample peak of the result is at most c (1 + 2^-22); an isolated peak comes out at the
+ * ceiling; dense over-ceiling material can overshoot in true peak: follow
+ * with msg_truepeak + msg_truepeak_gain where the ceiling must hold. */
+typedef struct msg_limit_rec {
+    double min_gain, reduction_db;
+    int64_t limited_frames;
+    int32_t lookahead, state;
+} msg_limit_rec;
+/* Signals as for msg_truepeak.  tp_rec_dev: NULL, or the signals' device records measured by
+ * msg_truepeak on these samples: a signal whose true_peak <= c is then skipped (decided on
+ * the device; samples and records are the same with and without).  ceiling_tp not finite
+ * and positive, lookahead_frames < 1, sr < 1: MSG_E_VALUE; lookahead_frames > 4096:
+ * MSG_E_UNSUPPORTED.  rec_dev: n_signals device records.  The signals must not overlap.
+ * Enqueued on stream with no host synchronise; one call in flight per context. */
+int msg_limit(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+              int32_t n_signals, int32_t sr, double ceiling_tp, int32_t lookahead_frames,
+              const msg_truepeak_rec* tp_rec_dev, msg_limit_rec* rec_dev, void* stream);
+/* The same definition as one loop over one signal in host memory, in place (x: n frames of
+ * `channels` interleaved words); needs no device. */
+int msg_limit_host(float* x, int32_t channels, int64_t n, int32_t sr, double ceiling_tp,
+                   int32_t lookahead_frames, msg_limit_rec* rec);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
