@@ -333,6 +333,8 @@ struct msg_ctx {
     // (loudness.h), per-tile filter states, per-tile energy and peak
     DevBuf<int64_t> ld_meta;
     DevBuf<double> ld_tab, ld_state, ld_part;
+    // msg_loudness_range: the hop sums when the caller takes none, one double per short-term window
+    DevBuf<double> lr_hops, lr_win;
     // msg_truepeak / msg_truepeak_gain: the interpolator's taps (truepeak.h, uploaded once
     // by msg_create), signal extents + tile bases, per-tile maxima
     DevBuf<float> d_tp_tab;

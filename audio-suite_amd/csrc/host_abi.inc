@@ -1,12 +1,12 @@
 // host_abi.inc — the host-side entry points of the C ABI (include/msgpu.h): the record
 // sizes (msg_sizeof), the render plan (plan.h), the NumPy stream primitives (nprng.h) and
 // the host references of the render digest (digest.h), of the loudness and true-peak
-// measurements (loudness.h, truepeak.h), of the PCM quantiser (pcm.h) and of the look-ahead
+// measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantiser (pcm.h) and of the look-ahead
 // limiter (limit.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
-// named above (DigestPart / dg_host, LoudRec / ld_host, TruePeakRec / tp_host, PcmRec / pcm_host,
+// named above (DigestPart / dg_host, LoudRec / ld_host, LRangeRec / lr_host, TruePeakRec / tp_host, PcmRec / pcm_host,
 // LimitRec / lim_host).
 
 int64_t msg_sizeof(int32_t which) {
@@ -19,6 +19,7 @@ int64_t msg_sizeof(int32_t which) {
         case 5: return (int64_t)sizeof(msg_truepeak_rec);
         case 6: return (int64_t)sizeof(msg_pcm_rec);
         case 7: return (int64_t)sizeof(msg_limit_rec);
+        case 8: return (int64_t)sizeof(msg_lrange_rec);
         default: return -1;
     }
 }
@@ -129,6 +130,31 @@ int msg_loudness_host(const float* x, int32_t channels, int64_t n, int32_t sr, m
     LoudRec r;
     ld_host(x, channels, n, sr, &r);
     std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The loudness range and the maximum momentary / short-term loudness from given hop sums:
+// the definition of lrange.h in plain C++ (lr_hops_host)
+int msg_lrange_hops_host(const double* hops, int64_t n_hops, int64_t hop, msg_lrange_rec* rec) {
+    static_assert(sizeof(LRangeRec) == sizeof(msg_lrange_rec), "LRangeRec is msg_lrange_rec");
+    if (!rec || n_hops < 0 || hop < 1 || (n_hops > 0 && !hops)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    LRangeRec r;
+    lr_hops_host(hops, n_hops, hop, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The same of one signal in host memory: ld_host's loop, then lr_hops_host on its hop sums (lr_host)
+int msg_loudness_range_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_loudness_rec* loud_rec,
+                            msg_lrange_rec* range_rec) {
+    if (!range_rec || n < 0 || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    if (!ld_rate_ok(sr)) return fail(nullptr, MSG_E_VALUE, "the sample rate must be a multiple of 10, at least 4000");
+    LoudRec l;
+    LRangeRec r;
+    lr_host(x, channels, n, sr, &l, &r);
+    if (loud_rec) std::memcpy(loud_rec, &l, sizeof(l));
+    std::memcpy(range_rec, &r, sizeof(r));
     return MSG_OK;
 }
 

@@ -23,6 +23,7 @@
 #include "host_pool.h"
 #include "digest.h"
 #include "loudness.h"
+#include "lrange.h"
 #include "truepeak.h"
 #include "pcm.h"
 #include "limit.h"
@@ -76,6 +77,10 @@ int msg_resample(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*
 }
 int msg_loudness(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, msg_loudness_rec*,
                  void*) {
+    return no_device();
+}
+int msg_loudness_range(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t,
+                       msg_loudness_rec*, msg_lrange_rec*, double*, const int64_t*, void*) {
     return no_device();
 }
 int msg_loudness_gain(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, msg_loudness_rec*, double,

@@ -193,6 +193,12 @@ hipError_t launch_resample(const RsPlan& p, int channels, unsigned tiles, hipStr
 // rate; state: 4 * channels doubles per tile; part: 2 doubles per tile (energy, peak)
 hipError_t launch_loudness(int n_sig, int channels, unsigned tiles, hipStream_t s, const float* x, const int64_t* meta,
                            int64_t hop, const double* tab, double* state, double* part, void* rec);
+// The same measurement, then the hop sums and the loudness-range records (kernels_lrange.h):
+// loud_rec may be null; meta carries two more rows of n_sig, each signal's first double in
+// hops (n / hop sums) and in win (one double per short-term window); range_rec: msg_lrange_rec records
+hipError_t launch_loudness_range(int n_sig, int channels, unsigned tiles, hipStream_t s, const float* x,
+                                 const int64_t* meta, int64_t hop, const double* tab, double* state, double* part,
+                                 void* loud_rec, double* hops, double* win, void* range_rec);
 // x *= (float)g per signal, g from its record; meta as above with tiles of LD_GAIN_TILE frames
 hipError_t launch_loudness_gain(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
                                 void* rec, double target, double ceiling);

@@ -153,8 +153,9 @@ inline void ld_table(int64_t sr, double* tab) {
 }
 
 // ---- the host reference: the definition as one sequential float64 loop ----------
-// x: n frames of `channels` interleaved float32 words
-inline void ld_host(const float* x, int channels, int64_t n, int64_t sr, LoudRec* rec) {
+// x: n frames of `channels` interleaved float32 words; hops_out: the n / hop hop sums too (lrange.h)
+inline void ld_host(const float* x, int channels, int64_t n, int64_t sr, LoudRec* rec,
+                    std::vector<double>* hops_out = nullptr) {
     double c[10];
     ld_kweight(sr, c);
     const int64_t hop = sr / 10, hops = n / hop, nb = ld_blocks(n, hop);
@@ -191,4 +192,5 @@ inline void ld_host(const float* x, int channels, int64_t n, int64_t sr, LoudRec
     rec->gain = 0.0;
     rec->n_blocks = (int32_t)nb;
     rec->n_kept = (int32_t)c2;
+    if (hops_out) hops_out->swap(hs);
 }

@@ -34,6 +34,7 @@
 #include "launch.h"
 #include "digest.h"
 #include "loudness.h"
+#include "lrange.h"
 #include "truepeak.h"
 #include "pcm.h"
 #include "limit.h"

@@ -1,6 +1,6 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
-// msg_loudness, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_limit.
+// msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_limit.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -173,6 +173,51 @@ int msg_loudness(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64
     if (const int rc = c.upload(ctx->ld_tab, tab)) return rc;
     HIPCHK(ctx, launch_loudness(n_signals, channels, (unsigned)c.tiles, c.s, x_dev, ctx->ld_meta.p, hop, ctx->ld_tab.p,
                                 ctx->ld_state.p, ctx->ld_part.p, rec_dev));
+    return c.finish();
+}
+
+int msg_loudness_range(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                       int32_t n_signals, int32_t sr, msg_loudness_rec* loud_rec_dev, msg_lrange_rec* range_rec_dev,
+                       double* hops_dev, const int64_t* hop_offsets, void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && range_rec_dev && (!hops_dev || hop_offsets), n_signals, channels))
+        return rc;
+    if (!ld_rate_ok(sr)) return fail(ctx, MSG_E_VALUE, "the sample rate must be a multiple of 10, at least 4000");
+    if (const int rc = sig_aligned(ctx, channels, x_dev)) return rc;
+    if (n_signals == 0) return MSG_OK;
+    const int64_t hop = sr / 10;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, [hop](int64_t f) { return ld_tiles(f, hop); }, "signal", "loudness",
+                              (size_t)2 * n_signals))
+        return rc;
+    if (c.tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    // each signal's hop sums (the caller's places, else back to back in the context's buffer) and windows
+    int64_t* hop_row = c.extra_row(n_signals, 0);
+    int64_t* win_row = c.extra_row(n_signals, 1);
+    int64_t n_hops = 0, n_win = 0;
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    for (int i = 0; i < n_signals; ++i) {
+        const int64_t hops = n[i] / hop;
+        if (hops_dev && hop_offsets[i] < 0) return fail(ctx, MSG_E_ARG, "bad hop offset");
+        hop_row[i] = hops_dev ? hop_offsets[i] : n_hops;
+        win_row[i] = n_win;
+        if (hops_dev && hops > 0) ranges.emplace_back(hop_offsets[i], hop_offsets[i] + hops);
+        n_hops += hops;
+        n_win += lr_windows(hops);
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); ++i)
+        if (ranges[i].first < ranges[i - 1].second) return fail(ctx, MSG_E_VALUE, "hop ranges overlap");
+    std::vector<double> tab(LD_TAB_N);
+    ld_table(sr, tab.data());
+    if (const int rc = c.open(ctx->ld_meta)) return rc;
+    HIPCHK(ctx, ctx->ld_state.ensure(c.parts() * 4 * channels));
+    HIPCHK(ctx, ctx->ld_part.ensure(c.parts() * 2));
+    if (!hops_dev) HIPCHK(ctx, ctx->lr_hops.ensure((size_t)std::max<int64_t>(1, n_hops)));
+    HIPCHK(ctx, ctx->lr_win.ensure((size_t)std::max<int64_t>(1, n_win)));
+    if (const int rc = c.upload(ctx->ld_tab, tab)) return rc;
+    HIPCHK(ctx, launch_loudness_range(n_signals, channels, (unsigned)c.tiles, c.s, x_dev, ctx->ld_meta.p, hop,
+                                      ctx->ld_tab.p, ctx->ld_state.p, ctx->ld_part.p, loud_rec_dev,
+                                      hops_dev ? hops_dev : ctx->lr_hops.p, ctx->lr_win.p, range_rec_dev));
     return c.finish();
 }
 

@@ -14,6 +14,7 @@ from .params import DEFAULTS, CONFIGS, config_params, merged  # noqa: F401
 # ``from msgpu.resample import design, ...``)
 from . import resample as _resample  # noqa: F401
 from . import loudness as _loudness  # noqa: F401  (the same for ``msgpu.loudness``)
+from . import lrange as _lrange  # noqa: F401
 from . import truepeak as _truepeak  # noqa: F401
 from . import pcm as _pcm  # noqa: F401
 from . import limit as _limit  # noqa: F401
@@ -26,7 +27,7 @@ def render(params, progress=None, device: int = 0):
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
                  out_lufs=None, out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf",
-                 out_dither_seed=0, out_limiter=None):
+                 out_dither_seed=0, out_limiter=None, out_report=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -45,10 +46,14 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     views of the packed byte tensor; ``out_dither`` "tpdf" or "none", from the stream
     (``out_dither_seed``, the preset's index in ``params_list``).  ``out_limiter``: hold
     ``out_true_peak`` with the look-ahead true-peak limiter (limit.py; one device only)
-    instead of one static gain: None off, True a 5 ms look-ahead, a number of milliseconds."""
+    instead of one static gain: None off, True a 5 ms look-ahead, a number of milliseconds.
+    ``out_report``: a list that gets one row per render with the EBU R 128 meters of what is
+    delivered (export.REPORT_DTYPE: lufs, lra, lo, hi, max_momentary, max_short, peak, true_peak,
+    dbtp, frames, rate; lrange.py; one device only, "audio" or "device")."""
     if devices is not None and len(list(devices)) > 1:
         from .export import Delivery
-        Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, limiter=out_limiter).one_device(
+        Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, limiter=out_limiter,
+                 report=out_report).one_device(
             "out_", len(list(devices)), companions=True)
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)
@@ -57,7 +62,7 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     from .dropin import render_batch as _rb
     return _rb(params_list, device, results, out_sr=out_sr, out_peak=out_peak, out_lufs=out_lufs,
                out_ceiling=out_ceiling, out_true_peak=out_true_peak, out_bits=out_bits, out_dither=out_dither,
-               out_dither_seed=out_dither_seed, out_limiter=out_limiter)
+               out_dither_seed=out_dither_seed, out_limiter=out_limiter, out_report=out_report)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):
@@ -100,6 +105,21 @@ def loudness(x, sr, device: int = 0):
     return _loudness.loudness(x, sr, device)
 
 
+def loudness_range(x, sr, device: int = 0):
+    """The EBU R 128 delivery meters of x, (n,) or (n, 2), at sr Hz from one measurement on the
+    device (see lrange.py): a dict with lufs, lra (EBU Tech 3342), lo, hi, max_momentary,
+    max_short (EBU Tech 3341) and gate.  NumPy in, floats out; a device tensor in,
+    one-element device tensors out with no host synchronise."""
+    return _lrange.loudness_range(x, sr, device)
+
+
+def loudness_curves(x, sr, device: int = 0):
+    """(momentary, short_term) loudness of x in LUFS at ten values per second, from the hop
+    sums the device measures (see lrange.py).  NumPy in, NumPy out; a device tensor in,
+    device tensors out with no host synchronise."""
+    return _lrange.loudness_curves(x, sr, device)
+
+
 def true_peak(x, sr, device: int = 0, db: bool = False):
     """BS.1770-4 true peak of x, (n,) or (n, 2), at sr Hz, measured on the device (see
     truepeak.py): linear, or dBTP with ``db``.  NumPy in, a float out; a device tensor in,
@@ -129,6 +149,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     ``export_peak`` deliver the variants at another sample rate, ``export_lufs`` /
     ``export_ceiling`` at a BS.1770 integrated loudness, ``export_true_peak`` under a
     ceiling in dBTP, ``export_bits`` as 16- or 24-bit PCM with TPDF dither, ``export_limiter`` holding
-    that ceiling with the look-ahead limiter (one device)."""
+    that ceiling with the look-ahead limiter, ``export_report`` with the EBU R 128 meters of every
+    delivered variant in a list and, with a folder, in loudness_report.csv (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

@@ -105,6 +105,12 @@ class MsgLimitRec(C.Structure):
                 ("lookahead", C.c_int32), ("state", C.c_int32)]
 
 
+class MsgLRangeRec(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("lra", "lo", "hi", "max_momentary", "max_short", "gate", "z_lo", "z_hi",
+                                          "z_max_m", "z_max_s")] + \
+               [(k, C.c_int32) for k in ("n_momentary", "n_short", "n_abs", "n_kept")]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -146,6 +152,11 @@ _PROTOS = {
     "msg_digest_host": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(MsgDigestRec)]),
     "msg_loudness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                                C.c_int32, C.c_void_p, C.c_void_p]),
+    "msg_loudness_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+                                     C.c_void_p]),
+    "msg_lrange_hops_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "msg_loudness_range_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "msg_loudness_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "msg_loudness_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
@@ -199,7 +210,7 @@ def lib() -> C.CDLL:
             if L.msg_abi_version() != ABI_VERSION:
                 raise RuntimeError("libmsgpu ABI version mismatch")
             for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec, MsgLoudnessRec,
-                                        MsgTruePeakRec, MsgPcmRec, MsgLimitRec)):
+                                        MsgTruePeakRec, MsgPcmRec, MsgLimitRec, MsgLRangeRec)):
                 if L.msg_sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmsgpu struct {st.__name__} size mismatch: "
                                        f"{L.msg_sizeof(which)} != {C.sizeof(st)}")

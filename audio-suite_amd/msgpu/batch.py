@@ -131,7 +131,8 @@ def _chunks(items, frames_of):
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0,
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
                       export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
-                      export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None):
+                      export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None,
+                      export_report=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -173,14 +174,22 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     below it by that peak's excess.  None off, True a 5 ms look-ahead, a positive number
     that many milliseconds; a static trim after it holds the ceiling on dense material.
     Needs ``export_true_peak``.  One device only.
+
+    ``export_report``: a list that gets one row per variant (export.REPORT_DTYPE: lufs, lra,
+    lo, hi, max_momentary, max_short, peak, true_peak, dbtp, frames, rate), the EBU R 128
+    meters of the float32 variant as it is delivered, measured on the device after every level
+    rule and before the quantiser (lrange.py, truepeak.py); with ``folder``, the rows are also
+    written to ``loudness_report.csv`` there, one line per file name.  One device only.
     """
     from .pack import PackedBatch, out_frames
 
     from .export import Delivery, deliver, unpack_all
 
     delivery = Delivery(export_sr, export_peak, export_lufs, export_ceiling, export_true_peak, export_bits,
-                        export_dither, export_dither_seed, export_limiter)
-    delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False)
+                        export_dither, export_dither_seed, export_limiter, export_report)
+    delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False,
+                   rates=[merged(base_params)["base_sr"]])
+    first_row = len(export_report) if export_report is not None else 0
     if export_bits is not None:
         from .pcm import records, write_wav_pcm
     base = merged(base_params)
@@ -222,6 +231,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
         done += len(chunk)
         eng.torch.cuda.synchronize(eng.device)
         host = out.cpu().numpy()
+        delivery.flush_report()
         if export_bits is not None:
             if export_records is not None:
                 export_records.extend(records(rec))
@@ -230,4 +240,8 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
             audio = [host[off:off + n].copy() for off, n in zip(offsets, lens)]
         for key, a in zip(chunk, audio):
             emit(key, a)
+    if export_report is not None and folder is not None:
+        from .export import write_report_csv
+        write_report_csv(os.path.join(folder, "loudness_report.csv"), [name for name, _, _ in results],
+                         export_report[first_row:])
     return results

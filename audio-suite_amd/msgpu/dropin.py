@@ -94,7 +94,7 @@ def _out_peaks(params_list, out_peak):
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
                  out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
-                 out_limiter=None):
+                 out_limiter=None, out_report=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -111,11 +111,15 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     ("audio") or views of the packed byte tensor ("device").  ``out_limiter``: hold
     ``out_true_peak`` with the look-ahead limiter (export.limiter_packed) instead of one
     static gain, so a render with a stray peak keeps its loudness: None off, True a 5 ms
-    look-ahead, a positive number that many milliseconds."""
+    look-ahead, a positive number that many milliseconds.  ``out_report``: a list that gets one
+    row per render (export.REPORT_DTYPE: lufs, lra, lo, hi, max_momentary, max_short, peak,
+    true_peak, dbtp, frames, rate), metered on the device on the float32 render as it is
+    delivered, after every level rule and before the quantiser (export.report_packed); the
+    rows are read once the renders' copy has been waited for ("device": when the call returns)."""
     delivery = Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, out_dither, out_dither_seed,
-                        out_limiter)
-    delivery.check("out_", results)
+                        out_limiter, out_report)
     params_list = list(params_list)
+    delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)
     packed = PackedBatch(params_list)
     out = eng.render_packed(packed)
@@ -123,8 +127,10 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     y, off, lens, _ = deliver(eng, out, packed.offsets, packed.out_n, [merged(p)["base_sr"] for p in params_list],
                               delivery, peaks, range(len(params_list)))
     if results == "device":
+        delivery.flush_report()
         return [y[int(o):int(o) + int(n)] for o, n in zip(off, lens)]
     eng.torch.cuda.synchronize(eng.device)
+    delivery.flush_report()
     if results == "stats":
         from .multi import device_stats
         return device_stats(eng, out, packed.offsets, packed.out_n)

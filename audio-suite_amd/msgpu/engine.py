@@ -248,6 +248,33 @@ class Engine:
         self._signal_call(L.lib().msg_loudness, x, channels, off, cnt, sr, C.c_void_p(rec.data_ptr()), stream=stream)
         return rec
 
+    def loudness_range(self, x, offsets, lens, channels, sr, hops=False, stream=None):
+        """msg_loudness_range of signals lying in a device float32 tensor (as Engine.loudness):
+        one measurement for the integrated loudness and for the loudness range and the
+        maximum momentary / short-term loudness (lrange.py).  Returns (loud_rec, range_rec),
+        float64 device tensors (signals, 5) and (signals, 12) whose rows are msg_loudness_rec
+        and msg_lrange_rec (loudness.records / lrange.records read them on the host);
+        ``hops``: (loud_rec, range_rec, hop_sums, hop_offsets) with every signal's K-weighted
+        100 ms hop sums back to back in one float64 device tensor, signal i's lens[i] // (sr // 10)
+        sums from hop_offsets[i].  Enqueued on ``stream``, no host synchronise."""
+        torch = self.torch
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        sr = int(sr)
+        if sr < 4000 or sr % 10:
+            raise ValueError("the sample rate must be a multiple of 10, at least 4000")
+        n = int(off.size)
+        loud = torch.empty((n, 5), dtype=torch.float64, device=x.device)
+        rng = torch.empty((n, 12), dtype=torch.float64, device=x.device)
+        n_hops = cnt // (sr // 10)
+        hop_off = (np.cumsum(n_hops) - n_hops).astype(np.int64)
+        buf = torch.empty(max(int(n_hops.sum()), 1), dtype=torch.float64, device=x.device) if hops else None
+        self._signal_call(L.lib().msg_loudness_range, x, channels, off, cnt, sr, C.c_void_p(loud.data_ptr()),
+                          C.c_void_p(rng.data_ptr()), None if buf is None else C.c_void_p(buf.data_ptr()),
+                          hop_off.ctypes.data_as(_I64P), stream=stream)
+        if hops:
+            return loud, rng, buf[:int(n_hops.sum())], hop_off
+        return loud, rng
+
     def loudness_gain(self, x, offsets, lens, channels, rec, target_lufs, ceiling=None, stream=None):
         """msg_loudness_gain: scale each signal of x in place to ``target_lufs`` from its
         device record (Engine.loudness), the gain formed on the device; ``ceiling``: a

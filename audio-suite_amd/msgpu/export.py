@@ -1,17 +1,22 @@
-"""The delivery chain of a rendered batch: resample -> level -> quantise, in HBM.
+"""The delivery chain of a rendered batch: resample -> level -> report -> quantise, in HBM.
 
 ``render_batch`` (dropin.py, ``out_*`` options) and ``render_variations`` (batch.py,
 ``export_*`` options) describe what they deliver with one ``Delivery``, check it with
 ``Delivery.check`` and run it with ``deliver``; each pass works on the renders where
-they lie (resample.py, loudness.py, truepeak.py, limit.py, pcm.py) and nothing here synchronises.
+they lie (resample.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing here
+synchronises.
 A new export rule is a field of ``Delivery``, its lines in ``check`` and its step in
 ``deliver``.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
+
+# one row of a delivery report: the meters of a render as it is delivered (report_packed)
+REPORT_DTYPE = np.dtype([(k, "<f8") for k in ("lufs", "lra", "lo", "hi", "max_momentary", "max_short", "peak",
+                                              "true_peak", "dbtp")] + [("frames", "<i8"), ("rate", "<i8")])
 
 
 @dataclass
@@ -25,10 +30,19 @@ class Delivery:
     dither: object = "tpdf"
     dither_seed: int = 0
     limiter: object = None        # hold true_peak with the look-ahead limiter: None off, True 5 ms, a number of ms
+    report: object = None         # a list that gets one REPORT_DTYPE row per render, measured on what is delivered
+    _pending: list = field(default_factory=list, init=False, repr=False, compare=False)   # deliver's unread reports
 
     # the rules that work on one device only: (the rule, the option that comes with it, why)
     _ONE_DEVICE = (("sr", "peak", " (multi.py sizes its shared memory by out_n)"), ("lufs", "ceiling", ""),
-                   ("true_peak", None, ""), ("bits", None, ""), ("limiter", None, ""))
+                   ("true_peak", None, ""), ("bits", None, ""), ("limiter", None, ""), ("report", None, ""))
+
+    def flush_report(self):
+        """Read the reports ``deliver`` left on the device into ``report``, in render order;
+        the caller has waited for the renders' copy, so this waits for nothing new."""
+        for pending in self._pending:
+            self.report.extend(pending.rows())
+        self._pending.clear()
 
     def limiter_ms(self):
         """The limiter's look-ahead in milliseconds, None when it is off; ValueError for
@@ -43,7 +57,8 @@ class Delivery:
             raise ValueError("the limiter is None, True or a positive number of milliseconds")
         return float(v)
 
-    def one_device(self, prefix, n_devices, rules=("sr", "lufs", "true_peak", "bits", "limiter"), companions=False):
+    def one_device(self, prefix, n_devices, rules=("sr", "lufs", "true_peak", "bits", "limiter", "report"),
+                   companions=False):
         """NotImplementedError for the first of ``rules`` asked for on more than one device;
         ``companions``: a rule's companion option alone asks for it too (render_batch, which
         looks at the device count before it looks at the values)."""
@@ -54,10 +69,11 @@ class Delivery:
                 if rule in rules and asked:
                     raise NotImplementedError(f"{prefix}{rule} on more than one device{why}")
 
-    def check(self, prefix, results="audio", n_devices=1, numeric_peak=True):
+    def check(self, prefix, results="audio", n_devices=1, numeric_peak=True, rates=()):
         """The rule table, worded with the caller's option prefix ("out_" or "export_").
         ``results``: the result kind delivered; ``numeric_peak``: whether ``peak`` may be a
-        number (render_variations has one template preset and takes None or "preset").
+        number (render_variations has one template preset and takes None or "preset");
+        ``rates``: the rates the renders are made at, for the rules that meter the delivered rate.
         Runs before any device call."""
         p = prefix
         if results not in ("audio", "stats", "device"):
@@ -85,8 +101,18 @@ class Delivery:
             if self.true_peak is None:
                 raise ValueError(f"{p}limiter needs {p}true_peak")
         self.one_device(p, n_devices, ("limiter",))
+        if self.report is not None:
+            from .loudness import _check_rate
+            if not isinstance(self.report, list):
+                raise ValueError(f"{p}report must be None or a list")
+            for rate in ([self.sr] if self.sr is not None else rates):
+                try:
+                    _check_rate(rate)
+                except ValueError:
+                    raise ValueError(f"{p}report meters rates that are multiples of 10, at least 4000") from None
+        self.one_device(p, n_devices, ("report",))
         if results == "stats":
-            for rule in ("sr", "lufs", "true_peak", "bits", "limiter"):
+            for rule in ("sr", "lufs", "true_peak", "bits", "limiter", "report"):
                 if getattr(self, rule) is not None:
                     raise ValueError(f"{p}{rule} applies to results 'audio' or 'device'")
 
@@ -94,8 +120,10 @@ class Delivery:
 def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     """Run ``delivery`` over renders lying in a device tensor ((frames, 2) float32, render i
     at frame offsets[i] with lens[i] frames at rates[i] Hz): resampled to ``delivery.sr``
-    (``peaks``: resample_packed's), levelled at the rate delivered, quantised with the
-    dither streams (``delivery.dither_seed``, keys[i]).  Returns (tensor, offsets, lens,
+    (``peaks``: resample_packed's), levelled at the rate delivered, metered as delivered when
+    ``delivery.report`` is a list (report_packed; ``delivery.flush_report`` reads the rows once
+    the caller has waited for its copy), quantised with the dither streams
+    (``delivery.dither_seed``, keys[i]).  Returns (tensor, offsets, lens,
     rec): the float32 renders with frame offsets and lengths and None, or, quantised, the
     packed bytes with byte offsets and lengths and the device PCM records.  Enqueued on
     the current stream, no host synchronise."""
@@ -104,6 +132,8 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
         out, offsets, lens = resample_packed(eng, out, offsets, lens, rates, int(d.sr), peaks)
         rates = [int(d.sr)] * len(lens)
     _level(eng, out, offsets, lens, rates, d.lufs, d.ceiling, d.true_peak, d.limiter_ms())
+    if d.report is not None:
+        d._pending.append(report_packed(eng, out, offsets, lens, rates))
     if d.bits is None:
         return out, offsets, lens, None
     return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys)
@@ -248,6 +278,64 @@ def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak, limiter_ms=No
         loudness_packed(eng, y, offsets, lens, rates, lufs, ceiling, true_peak)
     elif true_peak is not None:
         truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling)
+
+
+class Report:
+    """The device records of one report_packed call, in render order; ``rows`` copies them to
+    the host as a REPORT_DTYPE array (it waits for them)."""
+
+    def __init__(self, loud, rng, tp, lens, rates):
+        self.loud, self.rng, self.tp = loud, rng, tp
+        self.lens, self.rates = np.asarray(lens, dtype=np.int64), np.asarray(rates, dtype=np.int64)
+
+    def rows(self):
+        from .loudness import records as loud_records
+        from .lrange import records as range_records
+        from .truepeak import records as tp_records
+        out = np.zeros(len(self.lens), dtype=REPORT_DTYPE)
+        if not len(out):
+            return out
+        loud, rng, tp = loud_records(self.loud), range_records(self.rng), tp_records(self.tp)
+        out["lufs"] = loud["lufs"]
+        for k in ("lra", "lo", "hi", "max_momentary", "max_short"):
+            out[k] = rng[k]
+        for k in ("peak", "true_peak", "dbtp"):
+            out[k] = tp[k]
+        out["frames"], out["rate"] = self.lens, self.rates
+        return out
+
+
+def report_packed(eng, y, offsets, lens, rates):
+    """The delivery meters of renders lying in a device tensor (as loudness_packed), as they are
+    delivered: per distinct rate one msg_loudness_range call (integrated loudness, loudness
+    range, maximum momentary and short-term loudness) and msg_truepeak (sample peak, true
+    peak, dBTP).  Changes no sample; returns a Report, no host synchronise."""
+    torch = eng.torch
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rates = [int(s) for s in rates]
+    n = len(rates)
+    loud, rng, tp = (torch.empty((n, w), dtype=torch.float64, device=y.device) for w in (5, 12, 5))
+    for rate in sorted(set(rates)):
+        idx = [i for i, s in enumerate(rates) if s == rate]
+        l, r = eng.loudness_range(y, offsets[idx], lens[idx], 2, rate)
+        t = eng.true_peak(y, offsets[idx], lens[idx], 2, rate)
+        if len(idx) == n:
+            loud, rng, tp = l, r, t
+            break
+        at = torch.as_tensor(idx, device=y.device)
+        loud[at], rng[at], tp[at] = l, r, t
+    return Report(loud, rng, tp, lens, rates)
+
+
+def write_report_csv(path, names, rows):
+    """``rows`` (REPORT_DTYPE) as a CSV with a header, one line per file name."""
+    import csv
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["file"] + list(REPORT_DTYPE.names))
+        for name, row in zip(names, rows):
+            w.writerow([name] + [repr(row[k].item()) for k in REPORT_DTYPE.names])
 
 
 def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=None):

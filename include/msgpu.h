@@ -15,6 +15,7 @@
  *   msg_digest       per-render checksums on the device         (MS:1585-1589)
  *   msg_resample     sample-rate conversion of renders in HBM     (no counterpart: SURVEY §0)
  *   msg_loudness     BS.1770 integrated loudness and LUFS gain in HBM (no counterpart)
+ *   msg_loudness_range  loudness range, maximum momentary / short-term loudness (no counterpart)
  *   msg_truepeak     BS.1770 true peak and a dBTP ceiling in HBM   (no counterpart)
  *   msg_quantize     16/24-bit PCM with TPDF dither, packed in HBM  (sf.write's subtype, MS:1589)
  *   msg_limit        look-ahead true-peak limiter in HBM            (no counterpart)
@@ -119,7 +120,8 @@ int         msg_abi_version(void);
  * MSGPU_HOST_THREADS, else the CPU affinity / LOCAL_WORLD_SIZE, at most 16. */
 int         msg_host_threads(void);
 /* sizeof of the ABI structs (0 msg_preset, 1 msg_event, 2 msg_plan_info, 3 msg_digest_rec,
- * 4 msg_loudness_rec, 5 msg_truepeak_rec, 6 msg_pcm_rec, 7 msg_limit_rec) for binding checks */
+ * 4 msg_loudness_rec, 5 msg_truepeak_rec, 6 msg_pcm_rec, 7 msg_limit_rec, 8 msg_lrange_rec) for
+ * binding checks */
 int64_t     msg_sizeof(int32_t which);
 msg_ctx*    msg_create(int device_ordinal);
 void        msg_destroy(msg_ctx* ctx);
@@ -316,6 +318,40 @@ int msg_loudness_gain(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_
 /* The same definition as a sequential float64 loop over one signal in host memory
  * (x: n frames of `channels` interleaved words); needs no device. */
 int msg_loudness_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_loudness_rec* rec);
+
+/* The meters an EBU R 128 delivery is checked with, from the same measurement
+ * (csrc/lrange.h holds the definition, DESIGN.md "Loudness range" the kernels): the
+ * maximum momentary (400 ms) and short-term (3 s, one window per 100 ms) loudness of EBU
+ * Tech 3341, both ungated, and the loudness range of EBU Tech 3342: of the short-term
+ * windows above -70 LUFS and above 20 LU under their mean, the 95th minus the 10th
+ * percentile by nearest rank.
+ *   lra            loudness range in LU, 0 when no window survives the gates
+ *   lo, hi         the two percentile levels, -inf then
+ *   max_momentary, max_short   -inf without a complete block / window
+ *   gate           the relative gate, -inf when no window passes -70
+ *   z_lo, z_hi, z_max_m, z_max_s   the mean squares those levels are formed from
+ *   n_momentary, n_short       complete blocks and windows
+ *   n_abs, n_kept              windows above -70, windows above both gates
+ * A signal's record does not depend on the batch it is measured in, and a repeated
+ * call gives the same bits. */
+typedef struct msg_lrange_rec {
+    double lra, lo, hi, max_momentary, max_short, gate, z_lo, z_hi, z_max_m, z_max_s;
+    int32_t n_momentary, n_short, n_abs, n_kept;
+} msg_lrange_rec;
+/* Signals as for msg_loudness, measured once.  loud_rec_dev: NULL, or n_signals records
+ * equal to the byte to msg_loudness's.  range_rec_dev: n_signals device records.
+ * hops_dev: NULL, or a device buffer of doubles that takes signal p's n[p] / (sr / 10)
+ * K-weighted hop sums (a hop's tiles added in order) from hops_dev + hop_offsets[p]
+ * (host array, the ranges disjoint).  Enqueued on stream. */
+int msg_loudness_range(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                       int32_t n_signals, int32_t sr, msg_loudness_rec* loud_rec_dev, msg_lrange_rec* range_rec_dev,
+                       double* hops_dev, const int64_t* hop_offsets, void* stream);
+/* The record from n_hops given hop sums of `hop` frames each, in plain C++; needs no device. */
+int msg_lrange_hops_host(const double* hops, int64_t n_hops, int64_t hop, msg_lrange_rec* rec);
+/* msg_loudness_host's loop over one signal in host memory, then msg_lrange_hops_host on
+ * its hop sums; loud_rec may be NULL. */
+int msg_loudness_range_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_loudness_rec* loud_rec,
+                            msg_lrange_rec* range_rec);
 
 /* ITU-R BS.1770-4 Annex 2 true peak of signals lying in HBM (csrc/truepeak.h holds the
  * definition, DESIGN.md "True peak" the kernels): the signal oversampled by 4 below
