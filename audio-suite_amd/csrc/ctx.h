@@ -376,6 +376,8 @@ struct msg_ctx {
     // msg_quantize: signal extents, tile bases, stream keys and output offsets; per-tile partials
     DevBuf<int64_t> pcm_meta;
     DevBuf<int4> pcm_part;
+    // msg_quantize_shaped: the same rows; its lanes write the records themselves
+    DevBuf<int64_t> pcm_shape_meta;
     // msg_limit: signal extents, both kernels' tile bases and the scratch offsets; the smoothing
     // weights; r of every frame; per envelope tile the NaN flag; per signal the state; per apply
     // tile the least gain and the count

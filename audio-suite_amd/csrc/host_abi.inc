@@ -1,7 +1,7 @@
 // host_abi.inc — the host-side entry points of the C ABI (include/msgpu.h): the record
 // sizes (msg_sizeof), the render plan (plan.h), the NumPy stream primitives (nprng.h) and
 // the host references of the render digest (digest.h), of the loudness and true-peak
-// measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantiser (pcm.h) and of the look-ahead
+// measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantisers (pcm.h, pcm_shape.h) and of the look-ahead
 // limiter (limit.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
@@ -183,6 +183,23 @@ int msg_quantize_host(const float* x, int32_t channels, int64_t n, int32_t bits,
     if (!pcm_dither_ok(dither)) return fail(nullptr, MSG_E_VALUE, "dither must be MSG_DITHER_NONE or MSG_DITHER_TPDF");
     PcmRec r;
     pcm_host(x, channels, n, bits, dither, seed, key, out, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The same with noise-shaped dither: the error-feedback loop of pcm_shape.h (pcm_shape_host), the
+// device's bytes and record to the bit
+int msg_quantize_shaped_host(const float* x, int32_t channels, int64_t n, int32_t bits, int32_t dither, int32_t shape,
+                             uint64_t seed, uint64_t key, void* out, msg_pcm_rec* rec) {
+    static_assert(PCM_SHAPE_E3 == MSG_SHAPE_E3 && PCM_SHAPE_LIPSHITZ5 == MSG_SHAPE_LIPSHITZ5 &&
+                  PCM_SHAPE_F9 == MSG_SHAPE_F9, "the shape codes");
+    if (!rec || n < 0 || (n > 0 && (!x || !out))) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    if (!pcm_bits_ok(bits)) return fail(nullptr, MSG_E_VALUE, "bits must be 16 or 24");
+    if (!pcm_dither_ok(dither)) return fail(nullptr, MSG_E_VALUE, "dither must be MSG_DITHER_NONE or MSG_DITHER_TPDF");
+    if (!pcm_shape_ok(shape)) return fail(nullptr, MSG_E_VALUE, "shape must be MSG_SHAPE_E3, MSG_SHAPE_LIPSHITZ5 or MSG_SHAPE_F9");
+    PcmRec r;
+    pcm_shape_host(x, channels, n, bits, dither, shape, seed, key, out, &r);
     std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }

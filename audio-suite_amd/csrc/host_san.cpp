@@ -26,6 +26,7 @@
 #include "lrange.h"
 #include "truepeak.h"
 #include "pcm.h"
+#include "pcm_shape.h"
 #include "limit.h"
 #include "../../include/msgpu.h"
 
@@ -97,6 +98,10 @@ int msg_truepeak_gain(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*,
 }
 int msg_quantize(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, uint64_t,
                  const uint64_t*, void*, const int64_t*, msg_pcm_rec*, void*) {
+    return no_device();
+}
+int msg_quantize_shaped(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, int32_t,
+                        uint64_t, const uint64_t*, void*, const int64_t*, msg_pcm_rec*, void*) {
     return no_device();
 }
 int msg_limit(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, double, int32_t,

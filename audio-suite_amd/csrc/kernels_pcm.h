@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pcm.h"
+#include "pcm_store.h"                     // pcm_store4: a lane's four packed words, the signal's end byte-exact
 #include "sig_tiles.h"
 
 // Four consecutive words of one lane, the first m of them inside the signal, quantised
@@ -37,28 +38,6 @@ MSG_DEV float4 pcm_shifted(float4 v, float4 u, int a) {
     if (a == 1) return make_float4(v.y, v.z, v.w, u.x);
     if (a == 2) return make_float4(v.z, v.w, u.x, u.y);
     return make_float4(v.w, u.x, u.y, u.z);
-}
-
-// The first m of a lane's four packed words stored at dst (4-byte aligned; 8-byte at 16
-// bits).  m = 4: one dwordx2 or dwordx3.  m < 4, the signal's end: whole dwords, then
-// its last partial dword in sub-dword stores, and not a byte more.
-template <int BITS>
-MSG_DEV void pcm_store4(const uint32_t pk[3], int m, unsigned char* __restrict__ dst) {
-    typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-    struct alignas(4) v3u { uint32_t a, b, c; };              // 12 bytes at a 4-byte address: one dwordx3
-    if (m == 4) {
-        if (BITS == 16) *reinterpret_cast<v2u*>(dst) = v2u{pk[0], pk[1]};
-        else *reinterpret_cast<v3u*>(dst) = v3u{pk[0], pk[1], pk[2]};
-        return;
-    }
-    const int nb = m * (BITS / 8), full = nb >> 2;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-        if (j < full) reinterpret_cast<uint32_t*>(dst)[j] = pk[j];
-    uint32_t last = full == 0 ? pk[0] : (full == 1 ? pk[1] : pk[2]);
-    unsigned char* tail = dst + 4 * full;
-    if (nb & 2) { *reinterpret_cast<uint16_t*>(tail) = (uint16_t)last; tail += 2; last >>= 16; }
-    if (nb & 1) *tail = (unsigned char)last;
 }
 
 MSG_DEV void pcm_acc_add(PcmAcc& a, const PcmAcc& b) {

@@ -217,6 +217,10 @@ hipError_t launch_truepeak_gain(int n_sig, int channels, unsigned tiles, hipStre
 // (pcm_tiles of the words), stream keys, output byte offsets; part: one int4 per tile
 hipError_t launch_pcm(int n_sig, int channels, int bits, int dither, unsigned tiles, hipStream_t s, const float* x,
                       const int64_t* meta, void* out, void* part, void* rec);
+// noise-shaped quantiser (kernels_pcm_shape.h): one lane per signal, waves of PCM_SHAPE_T signals,
+// each lane's record into rec.  meta as for launch_pcm (the tile bases unused); n_sig > 0
+hipError_t launch_pcm_shape(int n_sig, int channels, int bits, int dither, int shape, hipStream_t s, const float* x,
+                            const int64_t* meta, void* out, void* rec);
 
 // look-ahead true-peak limiter (kernels_limit.h): the envelope over env_tiles tiles of LIM_ENV_TILE
 // frames into rbuf and nanpart, one wave per signal into state, the apply over tiles of

@@ -37,6 +37,7 @@
 #include "lrange.h"
 #include "truepeak.h"
 #include "pcm.h"
+#include "pcm_shape.h"
 #include "limit.h"
 #include "host_pool.h"
 #include "er_merge.h"

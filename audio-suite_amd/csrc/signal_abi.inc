@@ -1,6 +1,6 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
-// msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_limit.
+// msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_quantize_shaped, msg_limit.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -306,6 +306,44 @@ int msg_quantize(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64
     HIPCHK(ctx, ctx->pcm_part.ensure(c.parts()));
     HIPCHK(ctx, launch_pcm(n_signals, channels, bits, dither, (unsigned)c.tiles, c.s, x_dev, ctx->pcm_meta.p, out_dev,
                            ctx->pcm_part.p, rec_dev));
+    return c.finish();
+}
+
+// msg_quantize with the error feedback of pcm_shape.h: the same arguments, checks and rows; one
+// lane per signal walks the signal's chain, so there are no tiles and no partials
+int msg_quantize_shaped(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                        int32_t n_signals, int32_t bits, int32_t dither, int32_t shape, uint64_t seed,
+                        const uint64_t* keys, void* out_dev, const int64_t* out_byte_off, msg_pcm_rec* rec_dev,
+                        void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && out_byte_off && rec_dev, n_signals, channels)) return rc;
+    if (!pcm_bits_ok(bits)) return fail(ctx, MSG_E_VALUE, "bits must be 16 or 24");
+    if (!pcm_dither_ok(dither)) return fail(ctx, MSG_E_VALUE, "dither must be MSG_DITHER_NONE or MSG_DITHER_TPDF");
+    if (!pcm_shape_ok(shape)) return fail(ctx, MSG_E_VALUE, "shape must be MSG_SHAPE_E3, MSG_SHAPE_LIPSHITZ5 or MSG_SHAPE_F9");
+    if ((reinterpret_cast<uintptr_t>(x_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
+        return fail(ctx, MSG_E_ARG, "the input must be 4-byte and the output 16-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, [](int64_t) { return (int64_t)0; }, "signal", "quantiser",
+                              (size_t)2 * n_signals))
+        return rc;
+    int64_t* key_row = c.extra_row(n_signals, 0);
+    int64_t* out_row = c.extra_row(n_signals, 1);
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    ranges.reserve((size_t)n_signals);
+    for (int i = 0; i < n_signals; ++i) {
+        const int64_t o = out_byte_off[i], b = pcm_bytes(n[i] * channels, bits);
+        if (o < 0 || (o & 15)) return fail(ctx, MSG_E_VALUE, "output offsets must be multiples of 16");
+        key_row[i] = (int64_t)pcm_stream_key(seed, keys ? keys[i] : (uint64_t)i);
+        out_row[i] = o;
+        if (b > 0) ranges.emplace_back(o, o + b);
+    }
+    if (!ranges.empty() && (!x_dev || !out_dev)) return fail(ctx, MSG_E_ARG, "null buffer");
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); ++i)
+        if (ranges[i].first < ranges[i - 1].second) return fail(ctx, MSG_E_VALUE, "output ranges overlap");
+    if (const int rc = c.open(ctx->pcm_shape_meta)) return rc;
+    HIPCHK(ctx, launch_pcm_shape(n_signals, channels, bits, dither, shape, c.s, x_dev, ctx->pcm_shape_meta.p, out_dev,
+                                 rec_dev));
     return c.finish();
 }
 

@@ -27,7 +27,7 @@ def render(params, progress=None, device: int = 0):
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
                  out_lufs=None, out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf",
-                 out_dither_seed=0, out_limiter=None, out_report=None):
+                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -49,12 +49,15 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     instead of one static gain: None off, True a 5 ms look-ahead, a number of milliseconds.
     ``out_report``: a list that gets one row per render with the EBU R 128 meters of what is
     delivered (export.REPORT_DTYPE: lufs, lra, lo, hi, max_momentary, max_short, peak, true_peak,
-    dbtp, frames, rate; lrange.py; one device only, "audio" or "device")."""
+    dbtp, frames, rate; lrange.py; one device only, "audio" or "device").  ``out_shape``: with
+    ``out_bits``, noise-shaped dither: "e3", "lipshitz5" or "f9" (pcm.py)."""
     if devices is not None and len(list(devices)) > 1:
         from .export import Delivery
         Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, limiter=out_limiter,
                  report=out_report).one_device(
             "out_", len(list(devices)), companions=True)
+        if out_shape is not None:                   # with out_bits it was refused above
+            raise ValueError("out_shape needs out_bits")
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)
     if devices is not None:
@@ -62,7 +65,7 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     from .dropin import render_batch as _rb
     return _rb(params_list, device, results, out_sr=out_sr, out_peak=out_peak, out_lufs=out_lufs,
                out_ceiling=out_ceiling, out_true_peak=out_true_peak, out_bits=out_bits, out_dither=out_dither,
-               out_dither_seed=out_dither_seed, out_limiter=out_limiter, out_report=out_report)
+               out_dither_seed=out_dither_seed, out_limiter=out_limiter, out_report=out_report, out_shape=out_shape)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):
@@ -135,12 +138,13 @@ def limit(x, sr, ceiling_dbtp=-1.0, lookahead_ms=5.0, device: int = 0):
     return _limit.limit(x, sr, ceiling_dbtp, lookahead_ms, device)
 
 
-def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0):
+def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0, shape=None):
     """x, (n,) or (n, 2) float32, as 16- or 24-bit PCM quantised on the device with TPDF
     dither (or "none") from the stream (seed, key); see pcm.py.  NumPy in, int16 (or
     int32 at 24 bits, sign-extended) out in x's shape; a device tensor in, the packed
-    device bytes out with no host synchronise."""
-    return _pcm.quantize(x, bits, dither, seed, key, device)
+    device bytes out with no host synchronise.  ``shape``: None, or "e3", "lipshitz5" or
+    "f9" for noise-shaped dither."""
+    return _pcm.quantize(x, bits, dither, seed, key, device, shape)
 
 
 def render_variations(base_params, seeds, unfolds, stretches, folder=None, device: int = 0, devices=None, **kw):
@@ -148,7 +152,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     shards the variants across GPUs as render_batch does; ``export_sr`` /
     ``export_peak`` deliver the variants at another sample rate, ``export_lufs`` /
     ``export_ceiling`` at a BS.1770 integrated loudness, ``export_true_peak`` under a
-    ceiling in dBTP, ``export_bits`` as 16- or 24-bit PCM with TPDF dither, ``export_limiter`` holding
+    ceiling in dBTP, ``export_bits`` as 16- or 24-bit PCM with TPDF dither (``export_shape``: noise-shaped), ``export_limiter`` holding
     that ceiling with the look-ahead limiter, ``export_report`` with the EBU R 128 meters of every
     delivered variant in a list and, with a folder, in loudness_report.csv (one device)."""
     from .batch import render_variations as _rv

@@ -170,6 +170,11 @@ _PROTOS = {
                                C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "msg_quantize_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
                                     C.c_void_p, C.c_void_p]),
+    "msg_quantize_shaped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64),
+                                      C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    "msg_quantize_shaped_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
+                                           C.c_uint64, C.c_void_p, C.c_void_p]),
     "msg_limit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                             C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "msg_limit_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_void_p]),

@@ -132,7 +132,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
                       export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
                       export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None,
-                      export_report=None):
+                      export_report=None, export_shape=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -180,13 +180,18 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     meters of the float32 variant as it is delivered, measured on the device after every level
     rule and before the quantiser (lrange.py, truepeak.py); with ``folder``, the rows are also
     written to ``loudness_report.csv`` there, one line per file name.  One device only.
+
+    ``export_shape``: with ``export_bits``, noise-shaped dither: "e3", "lipshitz5" or "f9"
+    (pcm.py, psychoacoustic curves for 44.1 / 48 kHz).  The streams and keys are those of
+    ``export_dither``; the total error of every word is fed back along its channel, one
+    chain per channel of each variant, so the bits still do not depend on how the batch is cut.
     """
     from .pack import PackedBatch, out_frames
 
     from .export import Delivery, deliver, unpack_all
 
     delivery = Delivery(export_sr, export_peak, export_lufs, export_ceiling, export_true_peak, export_bits,
-                        export_dither, export_dither_seed, export_limiter, export_report)
+                        export_dither, export_dither_seed, export_limiter, export_report).with_shape(export_shape)
     delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False,
                    rates=[merged(base_params)["base_sr"]])
     first_row = len(export_report) if export_report is not None else 0

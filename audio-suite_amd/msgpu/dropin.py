@@ -94,7 +94,7 @@ def _out_peaks(params_list, out_peak):
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
                  out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
-                 out_limiter=None, out_report=None):
+                 out_limiter=None, out_report=None, out_shape=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -115,9 +115,11 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     row per render (export.REPORT_DTYPE: lufs, lra, lo, hi, max_momentary, max_short, peak,
     true_peak, dbtp, frames, rate), metered on the device on the float32 render as it is
     delivered, after every level rule and before the quantiser (export.report_packed); the
-    rows are read once the renders' copy has been waited for ("device": when the call returns)."""
+    rows are read once the renders' copy has been waited for ("device": when the call returns).
+    ``out_shape``: with ``out_bits``, noise-shaped dither ("e3", "lipshitz5" or "f9", pcm.py): the
+    same streams, the error fed back along each channel of each render."""
     delivery = Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, out_dither, out_dither_seed,
-                        out_limiter, out_report)
+                        out_limiter, out_report).with_shape(out_shape)
     params_list = list(params_list)
     delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)

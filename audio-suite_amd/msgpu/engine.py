@@ -359,20 +359,23 @@ class Engine:
                           stream=stream)
         return rec
 
-    def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None):
+    def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None,
+                 shape=None):
         """msg_quantize of signals lying in a device float32 tensor (as Engine.true_peak):
         ``bits``-bit PCM (16 or 24) with ``dither`` ("tpdf" or "none") from the stream
         (seed, keys[i]) (keys None: key = i), packed little-endian with no padding.
         Returns ``(out, byte_offsets, rec)``: the device bytes (uint8; signal i at
         byte_offsets[i], each rounded up to a multiple of 16; ``out``: a tensor to write
         into instead of a new one), and the device records, an int64 tensor (signals, 4)
-        whose rows are msg_pcm_rec (pcm.records reads them on the host).  Enqueued on
-        ``stream``, no host synchronise."""
-        from .pcm import check_bits, dither_code
+        whose rows are msg_pcm_rec (pcm.records reads them on the host).  ``shape``: None,
+        or "e3", "lipshitz5" or "f9": msg_quantize_shaped, the same call with noise-shaped
+        dither.  Enqueued on ``stream``, no host synchronise."""
+        from .pcm import check_bits, dither_code, shape_code
         torch = self.torch
         channels, off, cnt = self._signals(x, offsets, lens, channels)
         bits = check_bits(bits)
         code = dither_code(dither)
+        scode = None if shape is None else shape_code(shape)
         n = int(off.size)
         nbytes = cnt * (channels * (bits // 8))
         byte_off = np.zeros(n, dtype=np.int64)
@@ -391,10 +394,13 @@ class Engine:
               out.data_ptr() % 16):
             raise ValueError("out must be a contiguous 16-byte aligned uint8 tensor on x's device, large enough")
         rec = torch.empty((n, 4), dtype=torch.int64, device=x.device)
-        self._signal_call(L.lib().msg_quantize, x, channels, off, cnt, bits, code,
-                          C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                          None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(out.data_ptr()),
-                          byte_off.ctypes.data_as(_I64P), C.c_void_p(rec.data_ptr()), stream=stream)
+        tail = (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(out.data_ptr()),
+                byte_off.ctypes.data_as(_I64P), C.c_void_p(rec.data_ptr()))
+        if scode is None:
+            self._signal_call(L.lib().msg_quantize, x, channels, off, cnt, bits, code, *tail, stream=stream)
+        else:
+            self._signal_call(L.lib().msg_quantize_shaped, x, channels, off, cnt, bits, code, scode, *tail, stream=stream)
         return out, byte_off, rec
 
     # ---- last-batch inspection -----------------------------------------

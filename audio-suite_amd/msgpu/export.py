@@ -32,6 +32,14 @@ class Delivery:
     limiter: object = None        # hold true_peak with the look-ahead limiter: None off, True 5 ms, a number of ms
     report: object = None         # a list that gets one REPORT_DTYPE row per render, measured on what is delivered
     _pending: list = field(default_factory=list, init=False, repr=False, compare=False)   # deliver's unread reports
+    # noise-shaped dither for ``bits``: None, "e3", "lipshitz5" or "f9".  An option of the quantiser,
+    # not a rule of its own: a plain attribute set by with_shape(), so the dataclass's fields stay the rules
+    shape = None
+
+    def with_shape(self, shape):
+        """This delivery with ``shape`` as the quantiser's noise shape (checked by ``check``)."""
+        self.shape = shape
+        return self
 
     # the rules that work on one device only: (the rule, the option that comes with it, why)
     _ONE_DEVICE = (("sr", "peak", " (multi.py sizes its shared memory by out_n)"), ("lufs", "ceiling", ""),
@@ -92,6 +100,14 @@ class Delivery:
             from .pcm import check_bits, dither_code
             check_bits(self.bits)
             dither_code(self.dither)
+        if self.shape is not None:
+            from .pcm import shape_code
+            if self.bits is None:
+                raise ValueError(f"{p}shape needs {p}bits")
+            try:
+                shape_code(self.shape)
+            except ValueError:
+                raise ValueError(f"{p}shape must be None, 'e3', 'lipshitz5' or 'f9'") from None
         self.one_device(p, n_devices, ("bits",))
         if self.limiter is not None:
             try:
@@ -136,7 +152,7 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
         d._pending.append(report_packed(eng, out, offsets, lens, rates))
     if d.bits is None:
         return out, offsets, lens, None
-    return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys)
+    return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys, d.shape)
 
 
 def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
@@ -338,14 +354,15 @@ def write_report_csv(path, names, rows):
             w.writerow([name] + [repr(row[k].item()) for k in REPORT_DTYPE.names])
 
 
-def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=None):
+def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=None, shape=None):
     """Renders lying in a device tensor (as loudness_packed) as ``bits``-bit PCM, quantised
     and packed on the device after every level rule (msg_quantize, pcm.py): render i
-    takes its dither from the stream (seed, keys[i]).  Returns the device byte tensor,
+    takes its dither from the stream (seed, keys[i]); ``shape``: noise-shaped dither
+    (msg_quantize_shaped).  Returns the device byte tensor,
     each render's byte offset and length in it, and the device records (no host synchronise)."""
     offsets = np.asarray(offsets, dtype=np.int64)
     lens = np.asarray(lens, dtype=np.int64)
-    out, byte_off, rec = eng.quantize(y, offsets, lens, 2, bits, dither, seed, keys)
+    out, byte_off, rec = eng.quantize(y, offsets, lens, 2, bits, dither, seed, keys, shape=shape)
     return out, byte_off, lens * (2 * (int(bits) // 8)), rec
 
 

@@ -8,6 +8,12 @@ The dither is a counter-based hash of ``(seed, key, w)`` alone, so a signal's by
 not depend on the batch it is quantised in.  The device and ``msg_quantize_host`` agree
 to the bit; :func:`quantize_reference` restates the definition in NumPy for the tests,
 and nothing on the product path uses it.
+
+``shape`` ("e3", "lipshitz5", "f9") adds noise shaping (msg_quantize_shaped):
+the total error of each word, dither included, is fed back through the shape's taps, one
+chain per channel from the signal's first word to its last, which moves the 16-bit floor
+out of the band where the ear is most sensitive.  :func:`quantize_shaped_host` and
+:func:`quantize_shaped_reference` are its host loop and its NumPy restatement.
 """
 from __future__ import annotations
 
@@ -22,6 +28,13 @@ from . import _lib as L
 G = 0x9E3779B97F4A7C15
 TILE = 4096
 DITHER = {"none": 0, "tpdf": 1}
+# csrc/pcm_shape.h: a shape's code (MSG_SHAPE_*) and its integer taps H_k = -llround(c_k 65536)
+SHAPES = {
+    "e3": (1, (-106365, 64356, -7143)),
+    "lipshitz5": (2, (-133235, 141885, -128385, 104202, -40298)),
+    "f9": (3, (-158073, 220856, -258015, 273547, -219742, 144507, -83952, 37290, -5551)),
+}
+SHAPE_CHUNK = 32
 
 # msg_pcm_rec as a numpy record
 PCM_DTYPE = np.dtype([("clipped", "<i8"), ("nan", "<i8"), ("q_min", "<i4"), ("q_max", "<i4"),
@@ -37,6 +50,21 @@ def dither_code(dither):
     if not isinstance(dither, (str, bool)) and dither in (0, 1):
         return int(dither)
     raise ValueError("dither must be 'tpdf' or 'none'")
+
+
+def shape_code(shape):
+    """"e3" / "lipshitz5" / "f9" (or MSG_SHAPE_E3 / _LIPSHITZ5 / _F9) as the ABI's code."""
+    if isinstance(shape, str) and shape in SHAPES:
+        return SHAPES[shape][0]
+    if not isinstance(shape, (str, bool)) and shape in (1, 2, 3):
+        return int(shape)
+    raise ValueError("shape must be 'e3', 'lipshitz5' or 'f9'")
+
+
+def shape_taps(shape):
+    """The integer taps H_1 .. H_K of a shape (int64)."""
+    code = shape_code(shape)
+    return np.array(next(h for c, h in SHAPES.values() if c == code), dtype=np.int64)
 
 
 def check_bits(bits):
@@ -63,15 +91,21 @@ def stream_key(seed, key):
     return int(_fmix64([(int(seed) & _M64) ^ inner])[0])
 
 
-def dither(seed, key, w):
-    """The dither values d(seed, key, w) of the word indices ``w`` (float64, exact
-    multiples of 2^-24 in (-1, 1))."""
+def dither_int(seed, key, w):
+    """a - b of the dither stream at the word indices ``w`` (int64, |a - b| < 2^24): the
+    dither in units of 2^-24 LSB."""
     w = np.asarray(w).astype(np.uint64)
     with np.errstate(over="ignore"):
         h = _fmix64(np.uint64(stream_key(seed, key)) + (w + np.uint64(1)) * np.uint64(G))
     a = (h & np.uint64(0xFFFFFF)).astype(np.int64)
     b = ((h >> np.uint64(32)) & np.uint64(0xFFFFFF)).astype(np.int64)
-    return (a - b).astype(np.float64) * 2.0 ** -24
+    return a - b
+
+
+def dither(seed, key, w):
+    """The dither values d(seed, key, w) of the word indices ``w`` (float64, exact
+    multiples of 2^-24 in (-1, 1))."""
+    return dither_int(seed, key, w).astype(np.float64) * 2.0 ** -24
 
 
 _dither_values = dither          # the functions below take a parameter named ``dither``
@@ -155,6 +189,82 @@ def quantize_host(x, bits, dither="tpdf", seed=0, key=0):
     return unpack(out, bits, a.shape), rec[0]
 
 
+def quantize_shaped_reference(xs, bits, dither="tpdf", shape="f9", seed=0, keys=None):
+    """The noise-shaped quantiser's definition (csrc/pcm_shape.h) in NumPy, for the tests:
+    a Python loop over the frames, vectorised over the channel runs of the signals ``xs``
+    (a list; signal i takes the stream (seed, keys[i]), keys None: key = i).  Returns
+    ``(qs, recs, max_e)``: per signal q and rec as quantize_reference gives them, and the
+    largest |E| fed back in any run."""
+    bits = check_bits(bits)
+    code = dither_code(dither)
+    H = shape_taps(shape)
+    K = H.size
+    S = float(1 << (bits - 1))
+    sig = [_signal(x) for x in xs]
+    keys = list(range(len(sig))) if keys is None else list(keys)
+    runs = [(i, c) for i, (a, ch) in enumerate(sig) for c in range(ch)]
+    nf = max([a.shape[0] for a, _ in sig], default=0)
+    V = np.zeros((len(runs), nf), dtype=np.float64)           # v = x S, exact
+    D = np.zeros((len(runs), nf), dtype=np.int64)
+    n = np.zeros(len(runs), dtype=np.int64)
+    for row, (i, c) in enumerate(runs):
+        a, ch = sig[i]
+        f = a.shape[0]
+        n[row] = f
+        V[row, :f] = a.reshape(f, ch)[:, c].astype(np.float64) * S
+        if code:
+            D[row, :f] = dither_int(seed, keys[i], np.arange(f, dtype=np.uint64) * np.uint64(ch) + np.uint64(c))
+    Rr = np.zeros((len(runs), nf), dtype=np.float64)           # r of every word
+    E = np.zeros((len(runs), K), dtype=np.int64)
+    max_e = 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        for f in range(nf):
+            A = E @ H
+            F = (A + 32768) >> 16
+            d = D[:, f]
+            y = V[:, f] + (F + d).astype(np.float64) * 2.0 ** -24
+            r = np.rint(y)
+            none = np.isnan(y) | (r < -S) | (r > S - 1)
+            t = np.where(none, 0.0, (r - y) * 2.0 ** 24)
+            e = np.where(f < n, np.rint(t).astype(np.int64) + np.where(none, 0, d), 0)
+            E[:, 1:] = E[:, :-1].copy()
+            E[:, 0] = e
+            max_e = max(max_e, int(np.abs(e).max()))
+            Rr[:, f] = r
+        nan = np.isnan(Rr)
+        clipped = (Rr < -S) | (Rr > S - 1)
+        Q = np.where(nan, 0.0, np.clip(Rr, -S, S - 1)).astype(np.int64)
+    qs, recs = [], []
+    for i, (a, ch) in enumerate(sig):
+        rows = [row for row, (j, _) in enumerate(runs) if j == i]
+        f = a.shape[0]
+        q = np.stack([Q[row, :f] for row in rows], axis=1)
+        rec = np.zeros(1, dtype=PCM_DTYPE)
+        rec["clipped"] = sum(int(clipped[row, :f].sum()) for row in rows)
+        rec["nan"] = sum(int(nan[row, :f].sum()) for row in rows)
+        if q.size:
+            rec["q_min"], rec["q_max"] = int(q.min()), int(q.max())
+        rec["bits"], rec["dither"] = bits, code
+        qs.append(q.astype(int_dtype(bits)).reshape(a.shape))
+        recs.append(rec[0])
+    return qs, recs, max_e
+
+
+def quantize_shaped_host(x, bits, dither="tpdf", shape="f9", seed=0, key=0):
+    """msg_quantize_shaped_host: the library's error-feedback loop on the host (no device),
+    the device's bytes to the bit; returns ``(q, rec)`` as quantize_host does."""
+    bits = check_bits(bits)
+    code = dither_code(dither)
+    scode = shape_code(shape)
+    a, channels = _signal(x)
+    out = np.zeros(a.size * (bits // 8), dtype=np.uint8)
+    rec = np.zeros(1, dtype=PCM_DTYPE)
+    L.check(L.lib().msg_quantize_shaped_host(a.ctypes.data_as(C.c_void_p), channels, int(a.shape[0]), bits, code, scode,
+                                             C.c_uint64(int(seed) & _M64), C.c_uint64(int(key) & _M64),
+                                             out.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p)), None)
+    return unpack(out, bits, a.shape), rec[0]
+
+
 def records(rec):
     """Device records (Engine.quantize) as a PCM_DTYPE array on the host; waits for them."""
     host = rec.cpu().numpy()
@@ -213,15 +323,18 @@ def read_wav_pcm(path):
     return unpack(data, bits).reshape(-1, ch), sr, bits
 
 
-def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0):
+def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0, shape=None):
     """x, (n,) mono or (n, 2) stereo float32, as ``bits``-bit PCM quantised on the device.
     NumPy in: int16 (16 bits) or int32 (24 bits, sign-extended) out, in x's shape.  A
     device tensor in: the packed device bytes (uint8, n * channels * bits / 8) out,
-    enqueued on the current stream (no host synchronise)."""
+    enqueued on the current stream (no host synchronise).  ``shape``: None, or "e3",
+    "lipshitz5" or "f9" for noise-shaped dither (msg_quantize_shaped)."""
     from .engine import default_engine
 
     bits = check_bits(bits)
     dither_code(dither)
+    if shape is not None:
+        shape_code(shape)
     eng = default_engine(device)
     torch = eng.torch
     on_host = not isinstance(x, torch.Tensor)
@@ -230,7 +343,7 @@ def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0):
     if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] not in (1, 2)):
         raise ValueError("x must be (n,) or (n, 2)")
     channels = 1 if t.dim() == 1 else int(t.shape[1])
-    out, _, _ = eng.quantize(t, [0], [int(t.shape[0])], channels, bits, dither, seed, [key])
+    out, _, _ = eng.quantize(t, [0], [int(t.shape[0])], channels, bits, dither, seed, [key], shape=shape)
     if not on_host:
         return out
     return unpack(out.cpu().numpy(), bits, tuple(t.shape))

@@ -18,6 +18,7 @@
  *   msg_loudness_range  loudness range, maximum momentary / short-term loudness (no counterpart)
  *   msg_truepeak     BS.1770 true peak and a dBTP ceiling in HBM   (no counterpart)
  *   msg_quantize     16/24-bit PCM with TPDF dither, packed in HBM  (sf.write's subtype, MS:1589)
+ *   msg_quantize_shaped  the same with noise-shaped dither (error feedback)  (no counterpart)
  *   msg_limit        look-ahead true-peak limiter in HBM            (no counterpart)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
@@ -421,6 +422,35 @@ int msg_quantize(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64
  * `channels` interleaved words; out: n channels bits / 8 bytes); needs no device. */
 int msg_quantize_host(const float* x, int32_t channels, int64_t n, int32_t bits, int32_t dither, uint64_t seed,
                       uint64_t key, void* out, msg_pcm_rec* rec);
+
+/* Noise-shaped dither: msg_quantize with error feedback (csrc/pcm_shape.h holds the
+ * definition, DESIGN.md 4h the kernel).  Words, S, the dither stream, the packing and
+ * msg_pcm_rec are msg_quantize's; dither is NONE (D = 0) or TPDF (D = a - b of the stream
+ * as the integer).  A shape has K taps c_k, noise transfer function 1 - sum c_k z^-k:
+ *   MSG_SHAPE_E3         1.623, -0.982, 0.109
+ *   MSG_SHAPE_LIPSHITZ5  2.033, -2.165, 1.959, -1.590, 0.6149
+ *   MSG_SHAPE_F9         2.412, -3.370, 3.937, -4.174, 3.353, -2.205, 1.281, -0.569, 0.0847
+ * (Lipshitz, Vanderkooy and Wannamaker; designed for 44.1 kHz); the definition is the
+ * integer table H_k = -llround(c_k 65536) of csrc/pcm_shape.h.  Each channel of each
+ * signal keeps its own history E_1 .. E_K, integers in units of 2^-24 LSB, 0 at the
+ * signal's first frame.  For word w:
+ *   A = sum_k H_k E_k (int64);  F = (A + 32768) >> 16 (arithmetic);  v = (double)x S;
+ *   y = v + (double)(F + D) 2^-24 (one float64 add);  r = rint(y), ties to even;
+ *   q, clipped, nan, q_min, q_max from r as in msg_quantize;
+ *   E_new = (r - y) 2^24 rounded to an integer, + D; 0 for a clipped or NaN word;
+ *   E_K .. E_2 = E_{K-1} .. E_1, E_1 = E_new.
+ * The delivered error is the shaped total error, dither included; |E| < 1.5 2^24 and the
+ * output lies within 1.5 (1 + sum |c_k|) LSB of v (33.6 LSB for F9).  A channel is one
+ * chain from its first word to its last: a signal's bytes depend on the signal, bits,
+ * dither, shape, seed and key alone.  Host and device agree to the bit.  Arguments and
+ * errors as for msg_quantize; a shape out of range: MSG_E_VALUE. */
+enum msg_shape { MSG_SHAPE_E3 = 1, MSG_SHAPE_LIPSHITZ5 = 2, MSG_SHAPE_F9 = 3 };
+int msg_quantize_shaped(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                        int32_t n_signals, int32_t bits, int32_t dither, int32_t shape, uint64_t seed,
+                        const uint64_t* keys, void* out_dev, const int64_t* out_byte_off, msg_pcm_rec* rec_dev,
+                        void* stream);
+int msg_quantize_shaped_host(const float* x, int32_t channels, int64_t n, int32_t bits, int32_t dither, int32_t shape,
+                             uint64_t seed, uint64_t key, void* out, msg_pcm_rec* rec);
 
 /* Look-ahead true-peak limiter of signals lying in HBM, in place (csrc/limit.h holds the
  * definition, DESIGN.md 4f the kernels).  Per frame: the envelope e, the larger of the
