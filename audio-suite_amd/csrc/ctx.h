@@ -386,6 +386,8 @@ struct msg_ctx {
     DevBuf<uint32_t> lim_nan;
     DevBuf<int32_t> lim_state;
     DevBuf<uint2> lim_part;
+    // msg_edges: signal extents and both kernels' tile bases (the records are the caller's)
+    DevBuf<int64_t> edg_meta;
 
     // What must come first and in this order; the members' destructors follow.
     ~msg_ctx() {

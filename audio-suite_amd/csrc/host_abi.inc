@@ -2,12 +2,12 @@
 // sizes (msg_sizeof), the render plan (plan.h), the NumPy stream primitives (nprng.h) and
 // the host references of the render digest (digest.h), of the loudness and true-peak
 // measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantisers (pcm.h, pcm_shape.h) and of the look-ahead
-// limiter (limit.h).  Included
+// limiter (limit.h) and of the edges pass (edges.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
 // named above (DigestPart / dg_host, LoudRec / ld_host, LRangeRec / lr_host, TruePeakRec / tp_host, PcmRec / pcm_host,
-// LimitRec / lim_host).
+// LimitRec / lim_host, EdgesRec / edg_host).
 
 int64_t msg_sizeof(int32_t which) {
     switch (which) {
@@ -20,6 +20,8 @@ int64_t msg_sizeof(int32_t which) {
         case 6: return (int64_t)sizeof(msg_pcm_rec);
         case 7: return (int64_t)sizeof(msg_limit_rec);
         case 8: return (int64_t)sizeof(msg_lrange_rec);
+        case 9: return (int64_t)sizeof(msg_edges_rec);
+        case 10: return (int64_t)sizeof(msg_edges_opts);
         default: return -1;
     }
 }
@@ -224,6 +226,42 @@ int msg_limit_host(float* x, int32_t channels, int64_t n, int32_t sr, double cei
     if (const int rc = lim_values(nullptr, sr, ceiling_tp, lookahead_frames)) return rc;
     LimitRec r;
     lim_host(x, channels, n, sr, (float)ceiling_tp, lookahead_frames, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The value checks msg_edges and msg_edges_host share, in their order
+static int edg_values(msg_ctx* ctx, const msg_edges_opts* o) {
+    static_assert(sizeof(EdgesRec) == sizeof(msg_edges_rec), "EdgesRec is msg_edges_rec");
+    static_assert(sizeof(EdgesOpts) == sizeof(msg_edges_opts), "EdgesOpts is msg_edges_opts");
+    static_assert(EDG_HEAD == MSG_EDGES_HEAD && EDG_TAIL == MSG_EDGES_TAIL && EDG_SILENT == MSG_EDGES_SILENT,
+                  "the side and flag codes");
+    static_assert(EDG_LINEAR == MSG_CURVE_LINEAR && EDG_HANN == MSG_CURVE_HANN && EDG_QSIN == MSG_CURVE_QSIN,
+                  "the curve codes");
+    if (o->sides < 0 || o->sides > (MSG_EDGES_HEAD | MSG_EDGES_TAIL))
+        return fail(ctx, MSG_E_VALUE, "sides must be 0 or a sum of MSG_EDGES_HEAD and MSG_EDGES_TAIL");
+    if (o->sides && (!std::isfinite(o->trim_db) || o->trim_db > 0.0))
+        return fail(ctx, MSG_E_VALUE, "the trim threshold must be a finite number of dB, at most 0");
+    if (o->curve != MSG_CURVE_LINEAR && o->curve != MSG_CURVE_HANN && o->curve != MSG_CURVE_QSIN)
+        return fail(ctx, MSG_E_VALUE, "curve must be MSG_CURVE_LINEAR, MSG_CURVE_HANN or MSG_CURVE_QSIN");
+    for (const int64_t v : {o->pre, o->post, o->fade_in, o->fade_out})
+        if (v < 0 || v > EDG_MAX_FRAMES) return fail(ctx, MSG_E_VALUE, "pads and fades must be frame counts from 0 up");
+    if (o->loop > EDG_MAX_FRAMES) return fail(ctx, MSG_E_VALUE, "the loop crossfade must be a frame count");
+    if (o->loop >= 0 && (o->fade_in > 0 || o->fade_out > 0))
+        return fail(ctx, MSG_E_VALUE, "a loop crossfade excludes fades: give one");
+    return MSG_OK;
+}
+
+// Trim, fades and loop crossfade of one signal in host memory, in place: the definition of
+// edges.h as one loop (edg_host), the device's samples and record to the bit
+int msg_edges_host(float* x, int32_t channels, int64_t n, const msg_edges_opts* opts, msg_edges_rec* rec) {
+    if (!rec || !opts || n < 0 || n > EDG_MAX_FRAMES || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    if (const int rc = edg_values(nullptr, opts)) return rc;
+    EdgesOpts o;
+    std::memcpy(&o, opts, sizeof(o));
+    EdgesRec r;
+    edg_host(x, channels, n, edg_par(o), &r);
     std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }

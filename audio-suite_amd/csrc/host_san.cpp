@@ -4,7 +4,7 @@
 // the host references of the render digest (digest.h, msg_digest_host) and of the
 // loudness and true-peak measurements (loudness.h, msg_loudness_host; truepeak.h,
 // msg_truepeak_host), of the PCM quantiser (pcm.h, msg_quantize_host) and of the
-// look-ahead limiter (limit.h, msg_limit_host),
+// look-ahead limiter (limit.h, msg_limit_host) and of the edges pass (edges.h, msg_edges_host),
 // compiled by g++ with -fsanitize=address,undefined into
 // msgpu/libmsgpu_hostsan.so.  The device entry points are stubs that fail with
 // MSG_E_DEVICE, so the ctypes binding (_lib.py) loads this library unchanged
@@ -28,6 +28,7 @@
 #include "pcm.h"
 #include "pcm_shape.h"
 #include "limit.h"
+#include "edges.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -106,6 +107,10 @@ int msg_quantize_shaped(msg_ctx*, const float*, int32_t, const int64_t*, const i
 }
 int msg_limit(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, double, int32_t,
               const msg_truepeak_rec*, msg_limit_rec*, void*) {
+    return no_device();
+}
+int msg_edges(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, const msg_edges_opts*, msg_edges_rec*,
+              void*) {
     return no_device();
 }
 #include "host_abi.inc"

@@ -232,3 +232,12 @@ void limit_init_attrs();
 hipError_t launch_limit(int n_sig, int channels, int os, unsigned env_tiles, unsigned tiles, hipStream_t s, float* x,
                         const int64_t* meta, const float* tab, float c32, int L, const float* w, const void* tp_rec,
                         float* rbuf, uint32_t* nanpart, int32_t* state, void* part, void* rec);
+
+// edges pass (kernels_edges.h): with a trim the records' first / last reset and the find over
+// find_tiles tiles of EDG_TILE frames, then one lane per signal forms the span, then the apply
+// over apply_tiles tiles of EDG_APPLY_TILE frames of the fade or crossfade regions in place.
+// meta: offsets, frames, n_sig + 1 first find tiles, n_sig + 1 first apply tiles
+// (edg_apply_tiles); rec: msg_edges_rec records
+struct EdgesPar;
+hipError_t launch_edges(int n_sig, int channels, unsigned find_tiles, unsigned apply_tiles, hipStream_t s, float* x,
+                        const int64_t* meta, const EdgesPar& par, void* rec);

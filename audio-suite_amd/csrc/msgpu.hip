@@ -39,6 +39,7 @@
 #include "pcm.h"
 #include "pcm_shape.h"
 #include "limit.h"
+#include "edges.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"

@@ -1,6 +1,7 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
-// msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_quantize_shaped, msg_limit.
+// msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_quantize_shaped, msg_limit,
+// msg_edges.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -383,5 +384,35 @@ int msg_limit(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offse
     HIPCHK(ctx, launch_limit(n_signals, channels, tp_os(sr), (unsigned)env_tiles, (unsigned)c.tiles, c.s, x_dev,
                              ctx->lim_meta.p, ctx->d_tp_tab.p, (float)ceiling_tp, L, ctx->lim_w.p, tp_rec_dev,
                              ctx->lim_r.p, ctx->lim_nan.p, ctx->lim_state.p, ctx->lim_part.p, rec_dev));
+    return c.finish();
+}
+
+int msg_edges(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n, int32_t n_signals,
+              const msg_edges_opts* opts, msg_edges_rec* rec_dev, void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && opts && rec_dev, n_signals, channels)) return rc;
+    if (const int rc = edg_values(ctx, opts)) return rc;
+    if (const int rc = sig_aligned(ctx, channels, x_dev)) return rc;
+    if (n_signals == 0) return MSG_OK;
+    EdgesOpts o;
+    std::memcpy(&o, opts, sizeof(o));
+    const EdgesPar par = edg_par(o);
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, [&par](int64_t f) { return par.sides ? edg_tiles(f) : (int64_t)0; },
+                              "signal", "edges", (size_t)n_signals + 1))
+        return rc;
+    // the apply kernel's own tiles, from bounds that need no measurement
+    int64_t* apply_row = c.extra_row(n_signals, 0);
+    int64_t apply_tiles = 0, frames = 0;
+    for (int i = 0; i < n_signals; ++i) {
+        apply_row[i] = apply_tiles;
+        apply_tiles += edg_apply_tiles(par, n[i]);
+        frames += n[i];
+    }
+    apply_row[n_signals] = apply_tiles;
+    if (apply_tiles > INT32_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "too many edges tiles");
+    if (frames > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    if (const int rc = c.open(ctx->edg_meta)) return rc;
+    HIPCHK(ctx, launch_edges(n_signals, channels, (unsigned)c.tiles, (unsigned)apply_tiles, c.s, x_dev, ctx->edg_meta.p,
+                             par, rec_dev));
     return c.finish();
 }

@@ -18,6 +18,8 @@ from . import lrange as _lrange  # noqa: F401
 from . import truepeak as _truepeak  # noqa: F401
 from . import pcm as _pcm  # noqa: F401
 from . import limit as _limit  # noqa: F401
+from . import edges as _edges  # noqa: F401
+from .edges import Edges  # noqa: F401
 
 
 def render(params, progress=None, device: int = 0):
@@ -27,7 +29,7 @@ def render(params, progress=None, device: int = 0):
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
                  out_lufs=None, out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf",
-                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None):
+                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None, out_edges=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -50,11 +52,13 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     ``out_report``: a list that gets one row per render with the EBU R 128 meters of what is
     delivered (export.REPORT_DTYPE: lufs, lra, lo, hi, max_momentary, max_short, peak, true_peak,
     dbtp, frames, rate; lrange.py; one device only, "audio" or "device").  ``out_shape``: with
-    ``out_bits``, noise-shaped dither: "e3", "lipshitz5" or "f9" (pcm.py)."""
+    ``out_bits``, noise-shaped dither: "e3", "lipshitz5" or "f9" (pcm.py).  ``out_edges``: an
+    edges.Edges, every render trimmed to the span that holds sound, faded, or looped before the
+    level rules (edges.py; one device only)."""
     if devices is not None and len(list(devices)) > 1:
         from .export import Delivery
         Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, limiter=out_limiter,
-                 report=out_report).one_device(
+                 report=out_report).with_edges(out_edges).one_device(
             "out_", len(list(devices)), companions=True)
         if out_shape is not None:                   # with out_bits it was refused above
             raise ValueError("out_shape needs out_bits")
@@ -65,7 +69,8 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     from .dropin import render_batch as _rb
     return _rb(params_list, device, results, out_sr=out_sr, out_peak=out_peak, out_lufs=out_lufs,
                out_ceiling=out_ceiling, out_true_peak=out_true_peak, out_bits=out_bits, out_dither=out_dither,
-               out_dither_seed=out_dither_seed, out_limiter=out_limiter, out_report=out_report, out_shape=out_shape)
+               out_dither_seed=out_dither_seed, out_limiter=out_limiter, out_report=out_report, out_shape=out_shape,
+               out_edges=out_edges)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):
@@ -138,6 +143,14 @@ def limit(x, sr, ceiling_dbtp=-1.0, lookahead_ms=5.0, device: int = 0):
     return _limit.limit(x, sr, ceiling_dbtp, lookahead_ms, device)
 
 
+def edges(x, sr, edges, device: int = 0):
+    """Shape the ends of x, (n,) or (n, 2), at sr Hz on the device with an edges.Edges: silence
+    trim, fades or a loop crossfade (see edges.py).  NumPy in: the shaped span as a new float32
+    array and its record out; a device tensor in: shaped in place with no host synchronise,
+    the device record tensor out."""
+    return _edges.edges(x, sr, edges, device)
+
+
 def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0, shape=None):
     """x, (n,) or (n, 2) float32, as 16- or 24-bit PCM quantised on the device with TPDF
     dither (or "none") from the stream (seed, key); see pcm.py.  NumPy in, int16 (or
@@ -154,6 +167,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     ``export_ceiling`` at a BS.1770 integrated loudness, ``export_true_peak`` under a
     ceiling in dBTP, ``export_bits`` as 16- or 24-bit PCM with TPDF dither (``export_shape``: noise-shaped), ``export_limiter`` holding
     that ceiling with the look-ahead limiter, ``export_report`` with the EBU R 128 meters of every
-    delivered variant in a list and, with a folder, in loudness_report.csv (one device)."""
+    delivered variant in a list and, with a folder, in loudness_report.csv, ``export_edges`` trimming,
+    fading or looping every variant's ends (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

@@ -111,6 +111,15 @@ class MsgLRangeRec(C.Structure):
                [(k, C.c_int32) for k in ("n_momentary", "n_short", "n_abs", "n_kept")]
 
 
+class MsgEdgesRec(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("first", "last", "start", "end", "fade_in", "fade_out", "loop", "flags")]
+
+
+class MsgEdgesOpts(C.Structure):
+    _fields_ = [("trim_db", C.c_double), ("sides", C.c_int32), ("curve", C.c_int32)] + \
+               [(k, C.c_int64) for k in ("pre", "post", "fade_in", "fade_out", "loop")]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -178,6 +187,9 @@ _PROTOS = {
     "msg_limit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                             C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "msg_limit_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_void_p]),
+    "msg_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                            C.POINTER(MsgEdgesOpts), C.c_void_p, C.c_void_p]),
+    "msg_edges_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(MsgEdgesOpts), C.c_void_p]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
@@ -215,7 +227,8 @@ def lib() -> C.CDLL:
             if L.msg_abi_version() != ABI_VERSION:
                 raise RuntimeError("libmsgpu ABI version mismatch")
             for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec, MsgLoudnessRec,
-                                        MsgTruePeakRec, MsgPcmRec, MsgLimitRec, MsgLRangeRec)):
+                                        MsgTruePeakRec, MsgPcmRec, MsgLimitRec, MsgLRangeRec, MsgEdgesRec,
+                                        MsgEdgesOpts)):
                 if L.msg_sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmsgpu struct {st.__name__} size mismatch: "
                                        f"{L.msg_sizeof(which)} != {C.sizeof(st)}")

@@ -132,7 +132,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
                       export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
                       export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None,
-                      export_report=None, export_shape=None):
+                      export_report=None, export_shape=None, export_edges=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -185,13 +185,21 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     (pcm.py, psychoacoustic curves for 44.1 / 48 kHz).  The streams and keys are those of
     ``export_dither``; the total error of every word is fed back along its channel, one
     chain per channel of each variant, so the bits still do not depend on how the batch is cut.
+
+    ``export_edges``: an edges.Edges: every variant's ends are shaped after the resampler and
+    before the level rules (edges.py): trimmed to the span that holds sound (``trim_db``,
+    ``pad_ms``), faded in and out (``fade_ms``, ``curve``) or its tail crossfaded into its head
+    as a seamless loop (``loop_ms``).  The files, the returned audio, the report's ``frames`` and
+    ``loudness_report.csv`` carry the delivered span; the meters and the ceiling hold on it, and
+    the dither counts from its first word.  One device only.
     """
     from .pack import PackedBatch, out_frames
 
     from .export import Delivery, deliver, unpack_all
 
     delivery = Delivery(export_sr, export_peak, export_lufs, export_ceiling, export_true_peak, export_bits,
-                        export_dither, export_dither_seed, export_limiter, export_report).with_shape(export_shape)
+                        export_dither, export_dither_seed, export_limiter, export_report).with_shape(export_shape) \
+        .with_edges(export_edges)
     delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False,
                    rates=[merged(base_params)["base_sr"]])
     first_row = len(export_report) if export_report is not None else 0
@@ -242,7 +250,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                 export_records.extend(records(rec))
             audio = unpack_all(host, offsets, lens, export_bits)
         else:
-            audio = [host[off:off + n].copy() for off, n in zip(offsets, lens)]
+            audio = [host[int(off):int(off) + int(n)].copy() for off, n in zip(offsets, lens)]
         for key, a in zip(chunk, audio):
             emit(key, a)
     if export_report is not None and folder is not None:

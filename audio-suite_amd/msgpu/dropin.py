@@ -26,7 +26,7 @@ import numpy as np
 
 from .engine import default_engine
 from .export import (Delivery, deliver, unpack_all,  # noqa: F401  (the packed passes stay importable from here)
-                     limiter_packed, loudness_packed, quantize_packed, resample_packed, truepeak_packed)
+                     edges_packed, limiter_packed, loudness_packed, quantize_packed, resample_packed, truepeak_packed)
 from .pack import PackedBatch, design_sr
 from .params import first_missing_key, merged
 
@@ -94,7 +94,7 @@ def _out_peaks(params_list, out_peak):
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
                  out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
-                 out_limiter=None, out_report=None, out_shape=None):
+                 out_limiter=None, out_report=None, out_shape=None, out_edges=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -117,9 +117,13 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     delivered, after every level rule and before the quantiser (export.report_packed); the
     rows are read once the renders' copy has been waited for ("device": when the call returns).
     ``out_shape``: with ``out_bits``, noise-shaped dither ("e3", "lipshitz5" or "f9", pcm.py): the
-    same streams, the error fed back along each channel of each render."""
+    same streams, the error fed back along each channel of each render.  ``out_edges``: an
+    edges.Edges, the ends of every render shaped after the resampler and before the level rules
+    (export.edges_packed): trimmed to the span that holds sound, faded in and out, or its tail
+    crossfaded into its head as a loop.  The arrays, tensors, reports and dither streams are then
+    those of the span; a trim or a loop costs the chain one host wait for the spans."""
     delivery = Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, out_dither, out_dither_seed,
-                        out_limiter, out_report).with_shape(out_shape)
+                        out_limiter, out_report).with_shape(out_shape).with_edges(out_edges)
     params_list = list(params_list)
     delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)

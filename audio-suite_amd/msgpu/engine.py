@@ -359,6 +359,20 @@ class Engine:
                           stream=stream)
         return rec
 
+    def edges(self, x, offsets, lens, channels, sr, edges, stream=None):
+        """msg_edges: silence trim, fades or loop crossfade (edges.Edges, milliseconds taken at
+        ``sr`` Hz) over signals lying in a device float32 tensor (as Engine.true_peak), in
+        place; nothing is moved.  Returns the device records, an int64 tensor (signals, 8)
+        whose rows are msg_edges_rec (edges.records reads them on the host): signal i is
+        delivered from frame offsets[i] + start, end - start frames.  Enqueued on ``stream``,
+        no host synchronise."""
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        opts = edges.opts(sr)
+        rec = self.torch.empty((int(off.size), 8), dtype=self.torch.int64, device=x.device)
+        self._signal_call(L.lib().msg_edges, x, channels, off, cnt, C.byref(opts), C.c_void_p(rec.data_ptr()),
+                          stream=stream)
+        return rec
+
     def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None,
                  shape=None):
         """msg_quantize of signals lying in a device float32 tensor (as Engine.true_peak):

@@ -1,10 +1,12 @@
-"""The delivery chain of a rendered batch: resample -> level -> report -> quantise, in HBM.
+"""The delivery chain of a rendered batch: resample -> edges -> level -> report -> quantise, in HBM.
 
 ``render_batch`` (dropin.py, ``out_*`` options) and ``render_variations`` (batch.py,
 ``export_*`` options) describe what they deliver with one ``Delivery``, check it with
 ``Delivery.check`` and run it with ``deliver``; each pass works on the renders where
-they lie (resample.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing here
-synchronises.
+they lie (resample.py, edges.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing
+here synchronises, with one exception: an ``edges`` rule with a trim or a loop crossfade changes what
+is delivered of each render, so ``deliver`` reads the spans the device found (8 int64 per render)
+before it sizes the later passes.  That is the chain's one host wait; fades alone wait for nothing.
 A new export rule is a field of ``Delivery``, its lines in ``check`` and its step in
 ``deliver``.
 """
@@ -35,15 +37,25 @@ class Delivery:
     # noise-shaped dither for ``bits``: None, "e3", "lipshitz5" or "f9".  An option of the quantiser,
     # not a rule of its own: a plain attribute set by with_shape(), so the dataclass's fields stay the rules
     shape = None
+    # silence trim, fades or loop crossfade before the level rules: None or an edges.Edges.  A plain
+    # attribute as well, set by with_edges(): ``report`` stays the dataclass's last field
+    edges = None
 
     def with_shape(self, shape):
         """This delivery with ``shape`` as the quantiser's noise shape (checked by ``check``)."""
         self.shape = shape
         return self
 
+    def with_edges(self, edges):
+        """This delivery with ``edges`` (None or an edges.Edges) shaping every render's ends
+        after the resampler and before the level rules (checked by ``check``)."""
+        self.edges = edges
+        return self
+
     # the rules that work on one device only: (the rule, the option that comes with it, why)
     _ONE_DEVICE = (("sr", "peak", " (multi.py sizes its shared memory by out_n)"), ("lufs", "ceiling", ""),
-                   ("true_peak", None, ""), ("bits", None, ""), ("limiter", None, ""), ("report", None, ""))
+                   ("true_peak", None, ""), ("bits", None, ""), ("limiter", None, ""), ("report", None, ""),
+                   ("edges", None, ""))
 
     def flush_report(self):
         """Read the reports ``deliver`` left on the device into ``report``, in render order;
@@ -65,7 +77,7 @@ class Delivery:
             raise ValueError("the limiter is None, True or a positive number of milliseconds")
         return float(v)
 
-    def one_device(self, prefix, n_devices, rules=("sr", "lufs", "true_peak", "bits", "limiter", "report"),
+    def one_device(self, prefix, n_devices, rules=("sr", "lufs", "true_peak", "bits", "limiter", "report", "edges"),
                    companions=False):
         """NotImplementedError for the first of ``rules`` asked for on more than one device;
         ``companions``: a rule's companion option alone asks for it too (render_batch, which
@@ -127,8 +139,17 @@ class Delivery:
                 except ValueError:
                     raise ValueError(f"{p}report meters rates that are multiples of 10, at least 4000") from None
         self.one_device(p, n_devices, ("report",))
+        if self.edges is not None:
+            from .edges import Edges
+            if not isinstance(self.edges, Edges):
+                raise ValueError(f"{p}edges must be None or an Edges")
+            try:
+                self.edges.check()
+            except ValueError as e:
+                raise ValueError(f"{p}edges: {e}") from None
+        self.one_device(p, n_devices, ("edges",))
         if results == "stats":
-            for rule in ("sr", "lufs", "true_peak", "bits", "limiter", "report"):
+            for rule in ("sr", "lufs", "true_peak", "bits", "limiter", "report", "edges"):
                 if getattr(self, rule) is not None:
                     raise ValueError(f"{p}{rule} applies to results 'audio' or 'device'")
 
@@ -136,17 +157,21 @@ class Delivery:
 def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     """Run ``delivery`` over renders lying in a device tensor ((frames, 2) float32, render i
     at frame offsets[i] with lens[i] frames at rates[i] Hz): resampled to ``delivery.sr``
-    (``peaks``: resample_packed's), levelled at the rate delivered, metered as delivered when
+    (``peaks``: resample_packed's), its ends shaped by ``delivery.edges`` (edges_packed; from there
+    on a render is the span that rule left of it), levelled at the rate delivered, metered as delivered when
     ``delivery.report`` is a list (report_packed; ``delivery.flush_report`` reads the rows once
     the caller has waited for its copy), quantised with the dither streams
     (``delivery.dither_seed``, keys[i]).  Returns (tensor, offsets, lens,
     rec): the float32 renders with frame offsets and lengths and None, or, quantised, the
     packed bytes with byte offsets and lengths and the device PCM records.  Enqueued on
-    the current stream, no host synchronise."""
+    the current stream; no host synchronise, but for the spans of an ``edges`` rule that trims or
+    loops (the module's docstring)."""
     d = delivery
     if d.sr is not None:
         out, offsets, lens = resample_packed(eng, out, offsets, lens, rates, int(d.sr), peaks)
         rates = [int(d.sr)] * len(lens)
+    if d.edges is not None:
+        offsets, lens, _ = edges_packed(eng, out, offsets, lens, rates, d.edges)
     _level(eng, out, offsets, lens, rates, d.lufs, d.ceiling, d.true_peak, d.limiter_ms())
     if d.report is not None:
         d._pending.append(report_packed(eng, out, offsets, lens, rates))
@@ -194,6 +219,33 @@ def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
                 m = seg.abs().amax() if n else pk[i]
                 seg.mul_(torch.where(m > 0, pk[i] / m, torch.ones_like(m)))
     return y, y_off, y_lens
+
+
+def edges_packed(eng, y, offsets, lens, rates, edges):
+    """Shape the ends of renders lying in a device tensor ((frames, 2) float32, render i at frame
+    offsets[i] with lens[i] frames at rates[i] Hz) where they lie: msg_edges per distinct rate
+    (edges.py: the milliseconds of ``edges`` are frames at the render's rate).  Nothing is
+    moved.  Returns (offsets, lens, rec): where each render's delivered span lies, and the
+    device records in render order (engine.Engine.edges).  With a trim or a loop crossfade
+    the spans are read from the device, 8 int64 per render: the one host wait; otherwise the
+    extents come back as they were and nothing waits."""
+    from .edges import records
+    torch = eng.torch
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rates = [int(s) for s in rates]
+    rec = torch.empty((len(rates), 8), dtype=torch.int64, device=y.device)
+    for rate in sorted(set(rates)):
+        idx = [i for i, s in enumerate(rates) if s == rate]
+        r = eng.edges(y, offsets[idx], lens[idx], 2, rate, edges)
+        if len(idx) == len(rates):
+            rec = r
+            break
+        rec[torch.as_tensor(idx, device=y.device)] = r
+    if not edges.moves_span() or not len(rates):
+        return offsets, lens, rec
+    spans = records(rec)
+    return offsets + spans["start"], spans["end"] - spans["start"], rec
 
 
 def _per_rate(eng, y, offsets, lens, rates, level):

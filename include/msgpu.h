@@ -121,8 +121,8 @@ int         msg_abi_version(void);
  * MSGPU_HOST_THREADS, else the CPU affinity / LOCAL_WORLD_SIZE, at most 16. */
 int         msg_host_threads(void);
 /* sizeof of the ABI structs (0 msg_preset, 1 msg_event, 2 msg_plan_info, 3 msg_digest_rec,
- * 4 msg_loudness_rec, 5 msg_truepeak_rec, 6 msg_pcm_rec, 7 msg_limit_rec, 8 msg_lrange_rec) for
- * binding checks */
+ * 4 msg_loudness_rec, 5 msg_truepeak_rec, 6 msg_pcm_rec, 7 msg_limit_rec, 8 msg_lrange_rec,
+ * 9 msg_edges_rec, 10 msg_edges_opts) for binding checks */
 int64_t     msg_sizeof(int32_t which);
 msg_ctx*    msg_create(int device_ordinal);
 void        msg_destroy(msg_ctx* ctx);
@@ -486,6 +486,47 @@ int msg_limit(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offse
  * `channels` interleaved words); needs no device. */
 int msg_limit_host(float* x, int32_t channels, int64_t n, int32_t sr, double ceiling_tp,
                    int32_t lookahead_frames, msg_limit_rec* rec);
+
+/* Silence trim, fades and loop crossfade of signals lying in HBM, in place (csrc/edges.h holds
+ * the definition, DESIGN.md 4i the kernels).  A frame is sound when max over the channels of
+ * |x| >= (float)10^(trim_db / 20); a NaN is silence.  first / last are the lowest and highest
+ * sound frames and the span is [start, end):
+ *   start = max(0, first - pre) when sides has MSG_EDGES_HEAD, else 0
+ *   end   = min(n, last + 1 + post) when sides has MSG_EDGES_TAIL, else n
+ * sides = 0: no trim, nothing is searched (first = 0, last = n - 1).  No sound frame: first =
+ * last = -1, flags has MSG_EDGES_SILENT and the span is the whole signal.  Over the span's len
+ * frames, fade_in + fade_out > len shortens them to floor(len fade_in / (fade_in + fade_out))
+ * and the rest.  Frame k of a fade of F frames is scaled by (float)c((2 k + 1) / (2 F)),
+ * mirrored for the fade-out, in one float64 product rounded once; c is t, 1/2 - 1/2 cos(pi t)
+ * or sin(pi t / 2).  loop >= 0 (then both fades must be 0): X' = min(loop, len / 2) and
+ *   x[start + k] = x[start + k] c(t) + x[end - X' + k] c(1 - t),  t = (2 k + 1) / (2 X'),
+ * and the record's end is end - X', so that [start, end) repeats without a step.  Frames
+ * outside the fades keep their bits and nothing is moved: the caller reads the span.
+ *   first, last, start, end   frames; n = 0: every field is 0
+ *   fade_in, fade_out, loop   the frames as applied
+ * Host and device agree to the bit, samples and records; a signal's record does not depend on
+ * the batch it lies in.  All counts are frames; llround(ms sr / 1000) turns milliseconds into them. */
+enum msg_edges_side { MSG_EDGES_HEAD = 1, MSG_EDGES_TAIL = 2 };
+enum msg_edges_flag { MSG_EDGES_SILENT = 1 };
+enum msg_curve { MSG_CURVE_LINEAR = 0, MSG_CURVE_HANN = 1, MSG_CURVE_QSIN = 2 };
+typedef struct msg_edges_opts {
+    double trim_db;            /* finite and <= 0; read when sides != 0 */
+    int32_t sides, curve;
+    int64_t pre, post, fade_in, fade_out;
+    int64_t loop;              /* < 0: no crossfade */
+} msg_edges_opts;
+typedef struct msg_edges_rec {
+    int64_t first, last, start, end, fade_in, fade_out, loop, flags;
+} msg_edges_rec;
+/* Signals as for msg_truepeak, which must not overlap.  A value of opts out of range, or a
+ * loop together with a fade: MSG_E_VALUE.  rec_dev: n_signals device records.  The find and
+ * the apply enqueue back to back on stream with no host synchronise; one call in flight per
+ * context. */
+int msg_edges(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+              int32_t n_signals, const msg_edges_opts* opts, msg_edges_rec* rec_dev, void* stream);
+/* The same definition as one loop over one signal in host memory, in place (x: n frames of
+ * `channels` interleaved words); needs no device. */
+int msg_edges_host(float* x, int32_t channels, int64_t n, const msg_edges_opts* opts, msg_edges_rec* rec);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
