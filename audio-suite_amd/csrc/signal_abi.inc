@@ -84,6 +84,30 @@ struct SignalCall {
     size_t parts() const { return (size_t)std::max<int64_t>(1, tiles); }   // per-tile partials: never an empty buffer
 };
 
+// [first, last) ranges of bytes or elements the signals' outputs take: MSG_E_VALUE when two overlap
+using SigRanges = std::vector<std::pair<int64_t, int64_t>>;
+static int sig_disjoint(msg_ctx* ctx, SigRanges& ranges, const char* what) {
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); ++i)
+        if (ranges[i].first < ranges[i - 1].second) return fail(ctx, MSG_E_VALUE, std::string(what) + " ranges overlap");
+    return MSG_OK;
+}
+
+// The quantisers' extra rows: the stream keys (formed here for both paths) and the output offsets, 16-byte
+// aligned; ``ranges`` gets every signal's bytes.  The null test and sig_disjoint stay with each, in its order.
+static int pcm_rows(SignalCall& c, int32_t channels, const int64_t* n, int32_t n_signals, int32_t bits, uint64_t seed,
+                    const uint64_t* keys, const int64_t* out_byte_off, SigRanges& ranges) {
+    ranges.reserve((size_t)n_signals);
+    for (int i = 0; i < n_signals; ++i) {
+        const int64_t o = out_byte_off[i], b = pcm_bytes(n[i] * channels, bits);
+        if (o < 0 || (o & 15)) return fail(c.ctx, MSG_E_VALUE, "output offsets must be multiples of 16");
+        c.extra_row(n_signals, 0)[i] = (int64_t)pcm_stream_key(seed, keys ? keys[i] : (uint64_t)i);
+        c.extra_row(n_signals, 1)[i] = o;
+        if (b > 0) ranges.emplace_back(o, o + b);
+    }
+    return MSG_OK;
+}
+
 }  // extern "C++"
 
 int msg_digest(msg_ctx* ctx, const float* out_dev, const int64_t* out_offsets, const int64_t* out_n,
@@ -195,7 +219,7 @@ int msg_loudness_range(msg_ctx* ctx, const float* x_dev, int32_t channels, const
     int64_t* hop_row = c.extra_row(n_signals, 0);
     int64_t* win_row = c.extra_row(n_signals, 1);
     int64_t n_hops = 0, n_win = 0;
-    std::vector<std::pair<int64_t, int64_t>> ranges;
+    SigRanges ranges;
     for (int i = 0; i < n_signals; ++i) {
         const int64_t hops = n[i] / hop;
         if (hops_dev && hop_offsets[i] < 0) return fail(ctx, MSG_E_ARG, "bad hop offset");
@@ -205,9 +229,7 @@ int msg_loudness_range(msg_ctx* ctx, const float* x_dev, int32_t channels, const
         n_hops += hops;
         n_win += lr_windows(hops);
     }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); ++i)
-        if (ranges[i].first < ranges[i - 1].second) return fail(ctx, MSG_E_VALUE, "hop ranges overlap");
+    if (const int rc = sig_disjoint(ctx, ranges, "hop")) return rc;
     std::vector<double> tab(LD_TAB_N);
     ld_table(sr, tab.data());
     if (const int rc = c.open(ctx->ld_meta)) return rc;
@@ -288,21 +310,9 @@ int msg_quantize(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64
                               "quantiser", (size_t)2 * n_signals))
         return rc;
     if (c.tiles > 0 && (!x_dev || !out_dev)) return fail(ctx, MSG_E_ARG, "null buffer");
-    // the stream keys (formed here for both paths) and the output ranges: 16-byte aligned, disjoint
-    int64_t* key_row = c.extra_row(n_signals, 0);
-    int64_t* out_row = c.extra_row(n_signals, 1);
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    ranges.reserve((size_t)n_signals);
-    for (int i = 0; i < n_signals; ++i) {
-        const int64_t o = out_byte_off[i], b = pcm_bytes(n[i] * channels, bits);
-        if (o < 0 || (o & 15)) return fail(ctx, MSG_E_VALUE, "output offsets must be multiples of 16");
-        key_row[i] = (int64_t)pcm_stream_key(seed, keys ? keys[i] : (uint64_t)i);
-        out_row[i] = o;
-        if (b > 0) ranges.emplace_back(o, o + b);
-    }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); ++i)
-        if (ranges[i].first < ranges[i - 1].second) return fail(ctx, MSG_E_VALUE, "output ranges overlap");
+    SigRanges ranges;
+    if (const int rc = pcm_rows(c, channels, n, n_signals, bits, seed, keys, out_byte_off, ranges)) return rc;
+    if (const int rc = sig_disjoint(ctx, ranges, "output")) return rc;
     if (const int rc = c.open(ctx->pcm_meta)) return rc;
     HIPCHK(ctx, ctx->pcm_part.ensure(c.parts()));
     HIPCHK(ctx, launch_pcm(n_signals, channels, bits, dither, (unsigned)c.tiles, c.s, x_dev, ctx->pcm_meta.p, out_dev,
@@ -327,21 +337,10 @@ int msg_quantize_shaped(msg_ctx* ctx, const float* x_dev, int32_t channels, cons
     if (const int rc = c.rows(offsets, n, n_signals, [](int64_t) { return (int64_t)0; }, "signal", "quantiser",
                               (size_t)2 * n_signals))
         return rc;
-    int64_t* key_row = c.extra_row(n_signals, 0);
-    int64_t* out_row = c.extra_row(n_signals, 1);
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    ranges.reserve((size_t)n_signals);
-    for (int i = 0; i < n_signals; ++i) {
-        const int64_t o = out_byte_off[i], b = pcm_bytes(n[i] * channels, bits);
-        if (o < 0 || (o & 15)) return fail(ctx, MSG_E_VALUE, "output offsets must be multiples of 16");
-        key_row[i] = (int64_t)pcm_stream_key(seed, keys ? keys[i] : (uint64_t)i);
-        out_row[i] = o;
-        if (b > 0) ranges.emplace_back(o, o + b);
-    }
+    SigRanges ranges;
+    if (const int rc = pcm_rows(c, channels, n, n_signals, bits, seed, keys, out_byte_off, ranges)) return rc;
     if (!ranges.empty() && (!x_dev || !out_dev)) return fail(ctx, MSG_E_ARG, "null buffer");
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); ++i)
-        if (ranges[i].first < ranges[i - 1].second) return fail(ctx, MSG_E_VALUE, "output ranges overlap");
+    if (const int rc = sig_disjoint(ctx, ranges, "output")) return rc;
     if (const int rc = c.open(ctx->pcm_shape_meta)) return rc;
     HIPCHK(ctx, launch_pcm_shape(n_signals, channels, bits, dither, shape, c.s, x_dev, ctx->pcm_shape_meta.p, out_dev,
                                  rec_dev));

@@ -57,10 +57,11 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     level rules (edges.py; one device only)."""
     if devices is not None and len(list(devices)) > 1:
         from .export import Delivery
-        Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, limiter=out_limiter,
-                 report=out_report).with_edges(out_edges).one_device(
+        Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak, bits=out_bits,
+                 limiter=out_limiter, report=out_report, edges=out_edges).one_device(
             "out_", len(list(devices)), companions=True)
-        if out_shape is not None:                   # with out_bits it was refused above
+        # an option of out_bits and no rule of one_device's: with out_bits it was refused above
+        if out_shape is not None:
             raise ValueError("out_shape needs out_bits")
         from .multi import pool_for
         return pool_for(devices).render_batch(params_list, results=results)

@@ -197,9 +197,10 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
 
     from .export import Delivery, deliver, unpack_all
 
-    delivery = Delivery(export_sr, export_peak, export_lufs, export_ceiling, export_true_peak, export_bits,
-                        export_dither, export_dither_seed, export_limiter, export_report).with_shape(export_shape) \
-        .with_edges(export_edges)
+    delivery = Delivery(sr=export_sr, peak=export_peak, lufs=export_lufs, ceiling=export_ceiling,
+                        true_peak=export_true_peak, bits=export_bits, dither=export_dither,
+                        dither_seed=export_dither_seed, limiter=export_limiter, report=export_report,
+                        shape=export_shape, edges=export_edges)
     delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False,
                    rates=[merged(base_params)["base_sr"]])
     first_row = len(export_report) if export_report is not None else 0

@@ -122,8 +122,9 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     (export.edges_packed): trimmed to the span that holds sound, faded in and out, or its tail
     crossfaded into its head as a loop.  The arrays, tensors, reports and dither streams are then
     those of the span; a trim or a loop costs the chain one host wait for the spans."""
-    delivery = Delivery(out_sr, out_peak, out_lufs, out_ceiling, out_true_peak, out_bits, out_dither, out_dither_seed,
-                        out_limiter, out_report).with_shape(out_shape).with_edges(out_edges)
+    delivery = Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak,
+                        bits=out_bits, dither=out_dither, dither_seed=out_dither_seed, limiter=out_limiter,
+                        report=out_report, shape=out_shape, edges=out_edges)
     params_list = list(params_list)
     delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)

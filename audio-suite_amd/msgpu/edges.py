@@ -16,6 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
+from ._signal import device_signal, read_records
 
 # csrc/edges.h
 TILE = 4096              # frames per workgroup of the find kernel
@@ -239,8 +240,7 @@ def edges_host(x, sr, edges):
 
 def records(rec):
     """Device records (Engine.edges) as an EDGES_DTYPE array on the host; waits for them."""
-    host = rec.cpu().numpy()
-    return host.copy().view(EDGES_DTYPE).reshape(host.shape[0])
+    return read_records(rec, EDGES_DTYPE)
 
 
 def edges(x, sr, edges, device: int = 0):
@@ -252,12 +252,7 @@ def edges(x, sr, edges, device: int = 0):
 
     edges.check()
     eng = default_engine(device)
-    torch = eng.torch
-    on_host = not isinstance(x, torch.Tensor)
-    t = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).to(f"cuda:{eng.device}") if on_host else x
-    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] not in (1, 2)):
-        raise ValueError("x must be (n,) or (n, 2)")
-    channels = 1 if t.dim() == 1 else int(t.shape[1])
+    t, channels, on_host = device_signal(eng, x, in_place=True)
     rec = eng.edges(t, [0], [int(t.shape[0])], channels, int(sr), edges)
     if not on_host:
         return rec

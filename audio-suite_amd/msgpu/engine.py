@@ -13,6 +13,7 @@ import threading
 import numpy as np
 
 from . import _lib as L
+from .loudness import _check_rate      # the one loudness-rate check
 from .pack import PackedBatch
 
 
@@ -170,6 +171,11 @@ class Engine:
             raise ValueError(f"a {names[2]} extends past the {names[3]} tensor")
         return channels, off, cnt
 
+    def _record(self, rec, x, n, name, maker):
+        """The check of a record tensor a caller hands back: ``maker``'s float64 rows, one per signal."""
+        if rec.dtype != self.torch.float64 or not rec.is_contiguous() or rec.device != x.device or rec.numel() < 5 * n:
+            raise ValueError(f"{name} must be the float64 record tensor of Engine.{maker} on x's device")
+
     def _signal_call(self, fn, x, channels, off, cnt, *args, stream=None):
         """One per-signal entry point of the library, fn(ctx, x, [channels,] offsets, lens, n,
         *args, stream), on ``stream`` (None: the current stream of x's device) under the
@@ -241,9 +247,7 @@ class Engine:
         msg_loudness_rec (lufs, mean_sq, peak, gain, then n_blocks and n_kept as two
         int32; loudness.records reads them on the host), enqueued on ``stream``."""
         channels, off, cnt = self._signals(x, offsets, lens, channels)
-        sr = int(sr)
-        if sr < 4000 or sr % 10:
-            raise ValueError("the sample rate must be a multiple of 10, at least 4000")
+        sr = _check_rate(sr)
         rec = self.torch.empty((int(off.size), 5), dtype=self.torch.float64, device=x.device)
         self._signal_call(L.lib().msg_loudness, x, channels, off, cnt, sr, C.c_void_p(rec.data_ptr()), stream=stream)
         return rec
@@ -259,9 +263,7 @@ class Engine:
         sums from hop_offsets[i].  Enqueued on ``stream``, no host synchronise."""
         torch = self.torch
         channels, off, cnt = self._signals(x, offsets, lens, channels)
-        sr = int(sr)
-        if sr < 4000 or sr % 10:
-            raise ValueError("the sample rate must be a multiple of 10, at least 4000")
+        sr = _check_rate(sr)
         n = int(off.size)
         loud = torch.empty((n, 5), dtype=torch.float64, device=x.device)
         rng = torch.empty((n, 12), dtype=torch.float64, device=x.device)
@@ -280,11 +282,8 @@ class Engine:
         device record (Engine.loudness), the gain formed on the device; ``ceiling``: a
         linear sample peak no scaled signal may exceed (None: no limit).  Writes the
         gains into ``rec`` and returns it; enqueued on ``stream``, no host synchronise."""
-        torch = self.torch
         channels, off, cnt = self._signals(x, offsets, lens, channels)
-        n = int(off.size)
-        if rec.dtype != torch.float64 or not rec.is_contiguous() or rec.device != x.device or rec.numel() < 5 * n:
-            raise ValueError("rec must be the float64 record tensor of Engine.loudness on x's device")
+        self._record(rec, x, int(off.size), "rec", "loudness")
         ceil = 0.0 if ceiling is None else float(ceiling)
         if ceiling is not None and not ceil > 0.0:
             raise ValueError("the ceiling must be positive")
@@ -313,14 +312,12 @@ class Engine:
         is given, then held under ``ceiling_tp``, a linear true peak, and ``ceiling_peak``,
         a linear sample peak (None: no limit).  Writes the gains into ``tp_rec`` (and
         ``loud_rec``) and returns ``tp_rec``; enqueued on ``stream``, no host synchronise."""
-        torch = self.torch
         channels, off, cnt = self._signals(x, offsets, lens, channels)
         n = int(off.size)
-        for r, what in ((tp_rec, "tp_rec must be the float64 record tensor of Engine.true_peak on x's device"),
-                        (loud_rec, "loud_rec must be the float64 record tensor of Engine.loudness on x's device")):
-            if r is not None and (r.dtype != torch.float64 or not r.is_contiguous() or r.device != x.device or
-                                  r.numel() < 5 * n):
-                raise ValueError(what)
+        if tp_rec is not None:
+            self._record(tp_rec, x, n, "tp_rec", "true_peak")
+        if loud_rec is not None:
+            self._record(loud_rec, x, n, "loud_rec", "loudness")
         if tp_rec is None:
             raise ValueError("tp_rec must be the float64 record tensor of Engine.true_peak on x's device")
         if (loud_rec is None) != (target_lufs is None):
@@ -350,9 +347,8 @@ class Engine:
         if sr < 1:
             raise ValueError("the sample rate must be positive")
         n = int(off.size)
-        if tp_rec is not None and (tp_rec.dtype != torch.float64 or not tp_rec.is_contiguous() or
-                                   tp_rec.device != x.device or tp_rec.numel() < 5 * n):
-            raise ValueError("tp_rec must be the float64 record tensor of Engine.true_peak on x's device")
+        if tp_rec is not None:
+            self._record(tp_rec, x, n, "tp_rec", "true_peak")
         rec = torch.empty((n, 4), dtype=torch.float64, device=x.device)
         self._signal_call(L.lib().msg_limit, x, channels, off, cnt, sr, c, la,
                           None if tp_rec is None else C.c_void_p(tp_rec.data_ptr()), C.c_void_p(rec.data_ptr()),

@@ -7,8 +7,9 @@ they lie (resample.py, edges.py, loudness.py, truepeak.py, limit.py, lrange.py, 
 here synchronises, with one exception: an ``edges`` rule with a trim or a loop crossfade changes what
 is delivered of each render, so ``deliver`` reads the spans the device found (8 int64 per render)
 before it sizes the later passes.  That is the chain's one host wait; fades alone wait for nothing.
-A new export rule is a field of ``Delivery``, its lines in ``check`` and its step in
-``deliver``.
+A new export rule is a field of ``Delivery`` (after the last one, so the positional order stays),
+its row in ``RULES``, its lines in ``check`` and its step in ``deliver``; a pass that runs at the
+renders' rates is a closure handed to ``per_rate``.
 """
 from __future__ import annotations
 
@@ -19,6 +20,13 @@ import numpy as np
 # one row of a delivery report: the meters of a render as it is delivered (report_packed)
 REPORT_DTYPE = np.dtype([(k, "<f8") for k in ("lufs", "lra", "lo", "hi", "max_momentary", "max_short", "peak",
                                               "true_peak", "dbtp")] + [("frames", "<i8"), ("rate", "<i8")])
+
+# The rules, each a field of Delivery: (the rule, the option that comes with it, why it works on one
+# device only, whether results "stats" may ask for it).  ``dither``, ``dither_seed`` and ``shape`` are
+# options of ``bits`` that ask for nothing alone, so they have no row.
+RULES = (("sr", "peak", " (multi.py sizes its shared memory by out_n)", False), ("lufs", "ceiling", "", False),
+         ("true_peak", None, "", False), ("bits", None, "", False), ("limiter", None, "", False),
+         ("report", None, "", False), ("edges", None, "", False))
 
 
 @dataclass
@@ -33,29 +41,9 @@ class Delivery:
     dither_seed: int = 0
     limiter: object = None        # hold true_peak with the look-ahead limiter: None off, True 5 ms, a number of ms
     report: object = None         # a list that gets one REPORT_DTYPE row per render, measured on what is delivered
+    shape: object = None          # noise-shaped dither for ``bits``: None, "e3", "lipshitz5" or "f9"
+    edges: object = None          # silence trim, fades or loop crossfade before the level rules: an edges.Edges
     _pending: list = field(default_factory=list, init=False, repr=False, compare=False)   # deliver's unread reports
-    # noise-shaped dither for ``bits``: None, "e3", "lipshitz5" or "f9".  An option of the quantiser,
-    # not a rule of its own: a plain attribute set by with_shape(), so the dataclass's fields stay the rules
-    shape = None
-    # silence trim, fades or loop crossfade before the level rules: None or an edges.Edges.  A plain
-    # attribute as well, set by with_edges(): ``report`` stays the dataclass's last field
-    edges = None
-
-    def with_shape(self, shape):
-        """This delivery with ``shape`` as the quantiser's noise shape (checked by ``check``)."""
-        self.shape = shape
-        return self
-
-    def with_edges(self, edges):
-        """This delivery with ``edges`` (None or an edges.Edges) shaping every render's ends
-        after the resampler and before the level rules (checked by ``check``)."""
-        self.edges = edges
-        return self
-
-    # the rules that work on one device only: (the rule, the option that comes with it, why)
-    _ONE_DEVICE = (("sr", "peak", " (multi.py sizes its shared memory by out_n)"), ("lufs", "ceiling", ""),
-                   ("true_peak", None, ""), ("bits", None, ""), ("limiter", None, ""), ("report", None, ""),
-                   ("edges", None, ""))
 
     def flush_report(self):
         """Read the reports ``deliver`` left on the device into ``report``, in render order;
@@ -77,20 +65,20 @@ class Delivery:
             raise ValueError("the limiter is None, True or a positive number of milliseconds")
         return float(v)
 
-    def one_device(self, prefix, n_devices, rules=("sr", "lufs", "true_peak", "bits", "limiter", "report", "edges"),
-                   companions=False):
+    def one_device(self, prefix, n_devices, rules=tuple(r[0] for r in RULES), companions=False):
         """NotImplementedError for the first of ``rules`` asked for on more than one device;
         ``companions``: a rule's companion option alone asks for it too (render_batch, which
         looks at the device count before it looks at the values)."""
         if n_devices > 1:
-            for rule, companion, why in self._ONE_DEVICE:
+            for rule, companion, why, _ in RULES:
                 asked = getattr(self, rule) is not None or (companions and companion and
                                                             getattr(self, companion) is not None)
                 if rule in rules and asked:
                     raise NotImplementedError(f"{prefix}{rule} on more than one device{why}")
 
     def check(self, prefix, results="audio", n_devices=1, numeric_peak=True, rates=()):
-        """The rule table, worded with the caller's option prefix ("out_" or "export_").
+        """The rules' checks, worded with the caller's option prefix ("out_" or "export_"); their
+        order decides which exception wins, so a new rule's lines go last, before "stats".
         ``results``: the result kind delivered; ``numeric_peak``: whether ``peak`` may be a
         number (render_variations has one template preset and takes None or "preset");
         ``rates``: the rates the renders are made at, for the rules that meter the delivered rate.
@@ -149,8 +137,8 @@ class Delivery:
                 raise ValueError(f"{p}edges: {e}") from None
         self.one_device(p, n_devices, ("edges",))
         if results == "stats":
-            for rule in ("sr", "lufs", "true_peak", "bits", "limiter", "report", "edges"):
-                if getattr(self, rule) is not None:
+            for rule, _, _, with_stats in RULES:
+                if not with_stats and getattr(self, rule) is not None:
                     raise ValueError(f"{p}{rule} applies to results 'audio' or 'device'")
 
 
@@ -180,6 +168,36 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys, d.shape)
 
 
+def _extents(offsets, lens, rates):
+    return np.asarray(offsets, dtype=np.int64), np.asarray(lens, dtype=np.int64), [int(s) for s in rates]
+
+
+def rate_groups(rates):
+    """[(rate, the indices of its renders)], in ascending rate order."""
+    return [(rate, [i for i, s in enumerate(rates) if s == rate]) for rate in sorted(set(rates))]
+
+
+def per_rate(eng, y, offsets, lens, rates, pass_, cols, dtype=None):
+    """The one loop over rates: ``pass_(offsets, lens, rate)`` over the renders of each distinct
+    rate, in ascending rate order.  It enqueues the rate's library calls and returns their device
+    records, one tensor of ``cols`` columns or, ``cols`` a tuple, a tuple of them (``dtype``:
+    float64 when None); returns them in render order on y's device.  One rate: the pass's own
+    tensors, nothing allocated or scattered; no render: empty ones, the pass not called."""
+    torch = eng.torch
+    offsets, lens, rates = _extents(offsets, lens, rates)
+    groups = rate_groups(rates)
+    if len(groups) == 1:
+        return pass_(offsets, lens, groups[0][0])
+    many = isinstance(cols, tuple)
+    recs = [torch.empty((len(rates), w), dtype=dtype or torch.float64, device=y.device) for w in (cols if many else (cols,))]
+    for rate, idx in groups:
+        got = pass_(offsets[idx], lens[idx], rate)
+        at = torch.as_tensor(idx, device=y.device)
+        for rec, r in zip(recs, got if many else (got,)):
+            rec[at] = r
+    return tuple(recs) if many else recs[0]
+
+
 def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
     """Resample renders lying in a device output tensor ((frames, 2) float32, render i
     at frame offsets[i] with lens[i] frames at sr_in[i] Hz) to out_sr where they lie
@@ -191,15 +209,12 @@ def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
     reduction and one multiply over the batch."""
     from .resample import design, ratio, resample_len
     torch = eng.torch
-    offsets = np.asarray(offsets, dtype=np.int64)
-    lens = np.asarray(lens, dtype=np.int64)
-    rates = [int(s) for s in sr_in]
+    offsets, lens, rates = _extents(offsets, lens, sr_in)
     ratios = [ratio(s, out_sr) for s in rates]
     y_lens = np.array([resample_len(n, u, d) for n, (u, d) in zip(lens, ratios)], dtype=np.int64)
     y_off = np.concatenate([[0], np.cumsum(y_lens)[:-1]]).astype(np.int64)
     y = torch.empty((int(y_lens.sum()), 2), dtype=torch.float32, device=out.device)
-    for rate in sorted(set(rates)):
-        idx = [i for i, s in enumerate(rates) if s == rate]
+    for rate, idx in rate_groups(rates):
         up, down = ratio(rate, out_sr)
         h = design(up, down) if up != down else None
         if len(idx) == len(rates):            # one rate: the whole batch in one call
@@ -230,40 +245,13 @@ def edges_packed(eng, y, offsets, lens, rates, edges):
     the spans are read from the device, 8 int64 per render: the one host wait; otherwise the
     extents come back as they were and nothing waits."""
     from .edges import records
-    torch = eng.torch
-    offsets = np.asarray(offsets, dtype=np.int64)
-    lens = np.asarray(lens, dtype=np.int64)
-    rates = [int(s) for s in rates]
-    rec = torch.empty((len(rates), 8), dtype=torch.int64, device=y.device)
-    for rate in sorted(set(rates)):
-        idx = [i for i, s in enumerate(rates) if s == rate]
-        r = eng.edges(y, offsets[idx], lens[idx], 2, rate, edges)
-        if len(idx) == len(rates):
-            rec = r
-            break
-        rec[torch.as_tensor(idx, device=y.device)] = r
+    offsets, lens, rates = _extents(offsets, lens, rates)
+    rec = per_rate(eng, y, offsets, lens, rates, lambda off, cnt, rate: eng.edges(y, off, cnt, 2, rate, edges), 8,
+                   eng.torch.int64)
     if not edges.moves_span() or not len(rates):
         return offsets, lens, rec
     spans = records(rec)
     return offsets + spans["start"], spans["end"] - spans["start"], rec
-
-
-def _per_rate(eng, y, offsets, lens, rates, level):
-    """``level(offsets, lens, rate)`` over the renders of each distinct rate, in ascending
-    rate order: it measures and scales them and returns their device records (float64,
-    five columns); returns the records in render order."""
-    torch = eng.torch
-    offsets = np.asarray(offsets, dtype=np.int64)
-    lens = np.asarray(lens, dtype=np.int64)
-    rates = [int(s) for s in rates]
-    rec = torch.empty((len(rates), 5), dtype=torch.float64, device=y.device)
-    for rate in sorted(set(rates)):
-        idx = [i for i, s in enumerate(rates) if s == rate]
-        r = level(offsets[idx], lens[idx], rate)
-        if len(idx) == len(rates):
-            return r
-        rec[torch.as_tensor(idx, device=y.device)] = r
-    return rec
 
 
 def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None, true_peak=None):
@@ -283,7 +271,7 @@ def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None, tru
             t = eng.true_peak(y, off, cnt, 2, rate)
             eng.true_peak_gain(y, off, cnt, 2, t, r, float(target_lufs), _dbtp(true_peak), ceiling)
         return r
-    return _per_rate(eng, y, offsets, lens, rates, level)
+    return per_rate(eng, y, offsets, lens, rates, level, 5)
 
 
 def _dbtp(true_peak):
@@ -304,7 +292,7 @@ def truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling=None):
         t = eng.true_peak(y, off, cnt, 2, rate)
         eng.true_peak_gain(y, off, cnt, 2, t, None, None, _dbtp(true_peak), ceiling)
         return t
-    return _per_rate(eng, y, offsets, lens, rates, level)
+    return per_rate(eng, y, offsets, lens, rates, level, 5)
 
 
 def limiter_packed(eng, y, offsets, lens, rates, true_peak, lookahead_ms, lufs=None, ceiling=None):
@@ -317,15 +305,9 @@ def limiter_packed(eng, y, offsets, lens, rates, true_peak, lookahead_ms, lufs=N
     Works in place and returns the limiter's device records in render order
     (engine.Engine.limit); no host synchronise."""
     from .limit import lookahead_frames
-    torch = eng.torch
     c = _dbtp(true_peak)
-    offsets = np.asarray(offsets, dtype=np.int64)
-    lens = np.asarray(lens, dtype=np.int64)
-    rates = [int(s) for s in rates]
-    rec = torch.empty((len(rates), 4), dtype=torch.float64, device=y.device)
-    for rate in sorted(set(rates)):
-        idx = [i for i, s in enumerate(rates) if s == rate]
-        off, cnt = offsets[idx], lens[idx]
+
+    def level(off, cnt, rate):
         if lufs is not None:
             r = eng.loudness(y, off, cnt, 2, rate)
             eng.loudness_gain(y, off, cnt, 2, r, float(lufs), None)
@@ -333,10 +315,8 @@ def limiter_packed(eng, y, offsets, lens, rates, true_peak, lookahead_ms, lufs=N
         lim = eng.limit(y, off, cnt, 2, rate, c, lookahead_frames(rate, lookahead_ms), tp_rec=t)
         t2 = eng.true_peak(y, off, cnt, 2, rate)
         eng.true_peak_gain(y, off, cnt, 2, t2, None, None, c, ceiling)
-        if len(idx) == len(rates):
-            return lim
-        rec[torch.as_tensor(idx, device=y.device)] = lim
-    return rec
+        return lim
+    return per_rate(eng, y, offsets, lens, rates, level, 4)
 
 
 def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak, limiter_ms=None):
@@ -378,22 +358,9 @@ def report_packed(eng, y, offsets, lens, rates):
     delivered: per distinct rate one msg_loudness_range call (integrated loudness, loudness
     range, maximum momentary and short-term loudness) and msg_truepeak (sample peak, true
     peak, dBTP).  Changes no sample; returns a Report, no host synchronise."""
-    torch = eng.torch
-    offsets = np.asarray(offsets, dtype=np.int64)
-    lens = np.asarray(lens, dtype=np.int64)
-    rates = [int(s) for s in rates]
-    n = len(rates)
-    loud, rng, tp = (torch.empty((n, w), dtype=torch.float64, device=y.device) for w in (5, 12, 5))
-    for rate in sorted(set(rates)):
-        idx = [i for i, s in enumerate(rates) if s == rate]
-        l, r = eng.loudness_range(y, offsets[idx], lens[idx], 2, rate)
-        t = eng.true_peak(y, offsets[idx], lens[idx], 2, rate)
-        if len(idx) == n:
-            loud, rng, tp = l, r, t
-            break
-        at = torch.as_tensor(idx, device=y.device)
-        loud[at], rng[at], tp[at] = l, r, t
-    return Report(loud, rng, tp, lens, rates)
+    def meter(off, cnt, rate):
+        return eng.loudness_range(y, off, cnt, 2, rate) + (eng.true_peak(y, off, cnt, 2, rate),)
+    return Report(*per_rate(eng, y, offsets, lens, rates, meter, (5, 12, 5)), lens, rates)
 
 
 def write_report_csv(path, names, rows):

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._signal import device_signal, read_records
 from .truepeak import Z, _signal, oversampling, taps
 
 # csrc/limit.h
@@ -115,8 +116,7 @@ def limit_host(x, sr, ceiling_dbtp, lookahead_ms=5.0, lookahead=None):
 
 def records(rec):
     """Device records (Engine.limit) as a LIMIT_DTYPE array on the host; waits for them."""
-    host = rec.cpu().numpy()
-    return host.copy().view(LIMIT_DTYPE).reshape(host.shape[0])
+    return read_records(rec, LIMIT_DTYPE)
 
 
 def limit(x, sr, ceiling_dbtp=-1.0, lookahead_ms=5.0, device: int = 0):
@@ -129,12 +129,7 @@ def limit(x, sr, ceiling_dbtp=-1.0, lookahead_ms=5.0, device: int = 0):
     oversampling(sr)
     c = _ceiling(ceiling_dbtp)
     eng = default_engine(device)
-    torch = eng.torch
-    on_host = not isinstance(x, torch.Tensor)
-    t = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).to(f"cuda:{eng.device}") if on_host else x
-    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] not in (1, 2)):
-        raise ValueError("x must be (n,) or (n, 2)")
-    channels = 1 if t.dim() == 1 else int(t.shape[1])
+    t, channels, on_host = device_signal(eng, x, in_place=True)
     rec = eng.limit(t, [0], [int(t.shape[0])], channels, int(sr), c, lookahead_frames(sr, lookahead_ms))
     if not on_host:
         return rec

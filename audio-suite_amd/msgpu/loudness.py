@@ -16,6 +16,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._signal import device_signal, read_records
 
 # Tiles of the kernels (csrc/loudness.h): every hop of sr / 10 frames is cut into
 # tiles of TILE frames with a shorter last one, a tile into lane chunks of CHUNK frames.
@@ -128,8 +129,7 @@ def loudness_host(x, sr):
 
 def records(rec):
     """Device records (Engine.loudness) as a LOUDNESS_DTYPE array on the host; waits for them."""
-    host = rec.cpu().numpy()
-    return host.copy().view(LOUDNESS_DTYPE).reshape(host.shape[0])
+    return read_records(rec, LOUDNESS_DTYPE)
 
 
 def loudness(x, sr, device: int = 0):
@@ -140,13 +140,7 @@ def loudness(x, sr, device: int = 0):
 
     sr = _check_rate(sr)
     eng = default_engine(device)
-    torch = eng.torch
-    on_host = not isinstance(x, torch.Tensor)
-    t = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).to(f"cuda:{eng.device}") if on_host \
-        else x.contiguous()
-    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] not in (1, 2)):
-        raise ValueError("x must be (n,) or (n, 2)")
-    channels = 1 if t.dim() == 1 else int(t.shape[1])
+    t, channels, on_host = device_signal(eng, x)
     rec = eng.loudness(t, [0], [int(t.shape[0])], channels, sr)
     if not on_host:
         return rec[0, :1]

@@ -16,6 +16,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._signal import device_signal, read_records
 from .loudness import LOUDNESS_DTYPE, _biquad, _check_rate, kweight
 
 BLOCK_HOPS = 4          # momentary: 400 ms
@@ -143,18 +144,7 @@ def lrange_host(x, sr, loudness=False):
 def records(rec):
     """Device records (Engine.loudness_range's second tensor) as a LRANGE_DTYPE array on the
     host; waits for them."""
-    host = rec.cpu().numpy()
-    return host.copy().view(LRANGE_DTYPE).reshape(host.shape[0])
-
-
-def _device_signal(eng, x):
-    torch = eng.torch
-    on_host = not isinstance(x, torch.Tensor)
-    t = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).to(f"cuda:{eng.device}") if on_host \
-        else x.contiguous()
-    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] not in (1, 2)):
-        raise ValueError("x must be (n,) or (n, 2)")
-    return t, (1 if t.dim() == 1 else int(t.shape[1])), on_host
+    return read_records(rec, LRANGE_DTYPE)
 
 
 def loudness_range(x, sr, device: int = 0):
@@ -169,7 +159,7 @@ def loudness_range(x, sr, device: int = 0):
 
     sr = _check_rate(sr)
     eng = default_engine(device)
-    t, channels, on_host = _device_signal(eng, x)
+    t, channels, on_host = device_signal(eng, x)
     loud, rng = eng.loudness_range(t, [0], [int(t.shape[0])], channels, sr)
     names = ("lra", "lo", "hi", "max_momentary", "max_short", "gate")
     if not on_host:
@@ -193,7 +183,7 @@ def loudness_curves(x, sr, device: int = 0):
     sr = _check_rate(sr)
     eng = default_engine(device)
     torch = eng.torch
-    t, channels, on_host = _device_signal(eng, x)
+    t, channels, on_host = device_signal(eng, x)
     H = eng.loudness_range(t, [0], [int(t.shape[0])], channels, sr, hops=True)[2]
     hop = sr // 10
     if on_host:

@@ -23,6 +23,7 @@ import struct
 import numpy as np
 
 from . import _lib as L
+from ._signal import device_signal, read_records
 
 # csrc/pcm.h
 G = 0x9E3779B97F4A7C15
@@ -267,8 +268,7 @@ def quantize_shaped_host(x, bits, dither="tpdf", shape="f9", seed=0, key=0):
 
 def records(rec):
     """Device records (Engine.quantize) as a PCM_DTYPE array on the host; waits for them."""
-    host = rec.cpu().numpy()
-    return host.copy().view(PCM_DTYPE).reshape(host.shape[0])
+    return read_records(rec, PCM_DTYPE)
 
 
 def write_wav_pcm(path, q, sr, bits):
@@ -336,13 +336,7 @@ def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0, shape=No
     if shape is not None:
         shape_code(shape)
     eng = default_engine(device)
-    torch = eng.torch
-    on_host = not isinstance(x, torch.Tensor)
-    t = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).to(f"cuda:{eng.device}") if on_host \
-        else x.contiguous()
-    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] not in (1, 2)):
-        raise ValueError("x must be (n,) or (n, 2)")
-    channels = 1 if t.dim() == 1 else int(t.shape[1])
+    t, channels, on_host = device_signal(eng, x)
     out, _, _ = eng.quantize(t, [0], [int(t.shape[0])], channels, bits, dither, seed, [key], shape=shape)
     if not on_host:
         return out

@@ -16,6 +16,8 @@ import math
 
 import numpy as np
 
+from ._signal import device_signal
+
 ZEROS, BETA, ROLLOFF = 32, 12.0, 0.9
 
 # Output tiles of the kernels (csrc/resample.h).  Integer decimation by 2, 4 or 8
@@ -113,12 +115,7 @@ def resample(x, sr_in, sr_out, device: int = 0, **design_kw):
     up, down = ratio(sr_in, sr_out)
     eng = default_engine(device)
     torch = eng.torch
-    on_host = not isinstance(x, torch.Tensor)
-    t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(f"cuda:{eng.device}") if on_host \
-        else x.contiguous()
-    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] not in (1, 2)):
-        raise ValueError("x must be (n,) or (n, 2)")
-    channels = 1 if t.dim() == 1 else int(t.shape[1])
+    t, channels, on_host = device_signal(eng, x)
     n = int(t.shape[0])
     h = None
     if up != down:      # the limits first: a ratio beyond them would design millions of taps

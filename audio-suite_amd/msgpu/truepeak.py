@@ -16,6 +16,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._signal import device_signal, read_records
 
 # csrc/truepeak.h: zero crossings per side, taps per phase, positions per tile workgroup
 Z = 12
@@ -95,8 +96,7 @@ def true_peak_host(x, sr):
 
 def records(rec):
     """Device records (Engine.true_peak) as a TRUEPEAK_DTYPE array on the host; waits for them."""
-    host = rec.cpu().numpy()
-    return host.copy().view(TRUEPEAK_DTYPE).reshape(host.shape[0])
+    return read_records(rec, TRUEPEAK_DTYPE)
 
 
 def true_peak(x, sr, device: int = 0, db: bool = False):
@@ -107,13 +107,7 @@ def true_peak(x, sr, device: int = 0, db: bool = False):
 
     oversampling(sr)
     eng = default_engine(device)
-    torch = eng.torch
-    on_host = not isinstance(x, torch.Tensor)
-    t = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).to(f"cuda:{eng.device}") if on_host \
-        else x.contiguous()
-    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] not in (1, 2)):
-        raise ValueError("x must be (n,) or (n, 2)")
-    channels = 1 if t.dim() == 1 else int(t.shape[1])
+    t, channels, on_host = device_signal(eng, x)
     rec = eng.true_peak(t, [0], [int(t.shape[0])], channels, int(sr))
     col = 2 if db else 0
     if not on_host:

@@ -179,28 +179,32 @@ def test_delivery_rules(prefix):
 
     from msgpu.export import Delivery
     e = Edges(trim_db=-60, pad_ms=5, fade_ms=(2, 20))
-    d = Delivery(48000, None, -23.0, None, -1.0, 16).with_edges(e)
+    d = Delivery(48000, None, -23.0, None, -1.0, 16, edges=e)
     assert d.edges is e and Delivery().edges is None
     d.check(prefix)
-    Delivery().with_edges(e).check(prefix)                             # needs no other rule
-    Delivery().with_edges(None).check(prefix, "stats")
+    Delivery(edges=e).check(prefix)                             # needs no other rule
+    Delivery(edges=None).check(prefix, "stats")
     for bad in ("trim", -60, dict(trim_db=-60), True):
         with pytest.raises(VE, match=f"{prefix}edges must be None or an Edges"):
-            Delivery().with_edges(bad).check(prefix)
+            Delivery(edges=bad).check(prefix)
     for bad, word in ((Edges(trim_db=3), "trim_db"), (Edges(sides="left"), "sides"), (Edges(pad_ms=-1), "pad_ms"),
                       (Edges(fade_ms=(1, 2, 3)), "fade_ms"), (Edges(curve="cubic"), "curve"), (Edges(loop_ms=-2), "loop_ms"),
                       (Edges(loop_ms=10, fade_ms=5), "loop_ms and fade_ms")):
         with pytest.raises(VE, match=f"{prefix}edges: .*{word}"):
-            Delivery().with_edges(bad).check(prefix)
+            Delivery(edges=bad).check(prefix)
     with pytest.raises(VE, match=f"{prefix}edges applies to results"):
-        Delivery().with_edges(e).check(prefix, "stats")
+        Delivery(edges=e).check(prefix, "stats")
     with pytest.raises(NIE, match=f"{prefix}edges on more than one device"):
-        Delivery().with_edges(e).check(prefix, n_devices=2)
+        Delivery(edges=e).check(prefix, n_devices=2)
     with pytest.raises(NIE, match=f"{prefix}edges on more than one device"):
-        Delivery().with_edges(e).one_device(prefix, 2, companions=True)
-    Delivery().with_edges(None).one_device(prefix, 2, companions=True)
-    # the rule is a plain attribute: the dataclass's fields, and so every positional caller, stay as they were
-    assert [f.name for f in dataclasses.fields(Delivery) if f.init][-1] == "report"
+        Delivery(edges=e).one_device(prefix, 2, companions=True)
+    Delivery(edges=None).one_device(prefix, 2, companions=True)
+    # the rule is a field after the first ten: every positional caller stays as it was
+    names = [f.name for f in dataclasses.fields(Delivery) if f.init]
+    assert names[9] == "report" and names[10:] == ["shape", "edges"]
+    # and equality sees it: two deliveries that differ only in their edges are two deliveries
+    assert d != Delivery(48000, None, -23.0, None, -1.0, 16) and d == Delivery(48000, None, -23.0, None, -1.0, 16, edges=e)
+    assert d != dataclasses.replace(d, edges=Edges(trim_db=-50, pad_ms=5, fade_ms=(2, 20)))
 
 
 def test_front_ends_refuse_before_any_device_call():

@@ -160,7 +160,7 @@ def test_render_batch_with_edges(eng, sparse):
         assert np.array_equal(EC.bits(y), EC.bits(want))
     # batch independence: each render delivered alone, with its dither key, gives the same words
     for i, p in enumerate(sparse):
-        d = Delivery(48000, None, -23, None, -1, 16).with_edges(CHAIN)
+        d = Delivery(48000, None, -23, None, -1, 16, edges=CHAIN)
         packed = PackedBatch([p])
         y, off, nbytes, _ = deliver(eng, eng.render_packed(packed), packed.offsets, packed.out_n, [merged(p)["base_sr"]], d,
                                     None, [i])

@@ -162,19 +162,24 @@ def test_delivery_words_the_shape_rules_with_the_prefix():
     from msgpu.export import Delivery
     for prefix in ("out_", "export_"):
         with pytest.raises(VE, match=f"{prefix}shape needs {prefix}bits"):
-            Delivery().with_shape("f9").check(prefix)
+            Delivery(shape="f9").check(prefix)
         with pytest.raises(VE, match=f"{prefix}shape must be"):
-            Delivery(bits=16).with_shape("lipshitz").check(prefix)
+            Delivery(bits=16, shape="lipshitz").check(prefix)
         with pytest.raises(NIE, match=f"{prefix}bits on more than one"):
-            Delivery(bits=16).with_shape("e3").check(prefix, n_devices=2)
-    assert Delivery.shape is None and Delivery().shape is None and Delivery(bits=16).with_shape(None).shape is None
-    d = Delivery(bits=16).with_shape("f9")
+            Delivery(bits=16, shape="e3").check(prefix, n_devices=2)
+    assert Delivery.shape is None and Delivery().shape is None and Delivery(bits=16, shape=None).shape is None
+    d = Delivery(bits=16, shape="f9")
     d.check("out_")
     assert d.shape == "f9" and Delivery(bits=16).shape is None     # an instance's own, never the class's
-    Delivery(sr=48000, lufs=-23.0, true_peak=-1.0, bits=24).with_shape(2).check("export_")
+    Delivery(sr=48000, lufs=-23.0, true_peak=-1.0, bits=24, shape=2).check("export_")
     import dataclasses
     names = [f.name for f in dataclasses.fields(Delivery) if f.init]
-    assert names[-1] == "report" and "shape" not in names    # the rules and their positional order stand
+    # the first ten fields and their positional order stand; the newer rules are fields after them
+    assert names[:10] == ["sr", "peak", "lufs", "ceiling", "true_peak", "bits", "dither", "dither_seed", "limiter", "report"]
+    assert names[10:] == ["shape", "edges"]
+    # and equality, repr and replace see them
+    assert d != Delivery(bits=16) and d != Delivery(bits=16, shape="e3") and d == Delivery(bits=16, shape="f9")
+    assert "shape='f9'" in repr(d) and dataclasses.replace(d, bits=24).shape == "f9"
 
 
 # ---- what shaping is for -----------------------------------------------------------------------

@@ -97,7 +97,7 @@ def main():
             x.copy_(x0)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            y, off, nb, _ = deliver(eng, x, offs, lens, [sr] * S, Delivery(None, None, -23.0, None, -1.0, 16).with_edges(e),
+            y, off, nb, _ = deliver(eng, x, offs, lens, [sr] * S, Delivery(lufs=-23.0, true_peak=-1.0, bits=16, edges=e),
                                     None, range(S))
             torch.cuda.synchronize()
             if step >= a.warmup:
