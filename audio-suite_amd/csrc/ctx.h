@@ -388,6 +388,9 @@ struct msg_ctx {
     DevBuf<uint2> lim_part;
     // msg_edges: signal extents and both kernels' tile bases (the records are the caller's)
     DevBuf<int64_t> edg_meta;
+    // msg_filter: signal extents + tile bases, the cascade's table (filter.h), per-tile states
+    DevBuf<int64_t> fl_meta;
+    DevBuf<double> fl_tab, fl_state;
 
     // What must come first and in this order; the members' destructors follow.
     ~msg_ctx() {

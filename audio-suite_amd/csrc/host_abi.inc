@@ -2,12 +2,12 @@
 // sizes (msg_sizeof), the render plan (plan.h), the NumPy stream primitives (nprng.h) and
 // the host references of the render digest (digest.h), of the loudness and true-peak
 // measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantisers (pcm.h, pcm_shape.h) and of the look-ahead
-// limiter (limit.h) and of the edges pass (edges.h).  Included
+// limiter (limit.h), of the edges pass (edges.h) and of the delivery filter (filter.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
 // named above (DigestPart / dg_host, LoudRec / ld_host, LRangeRec / lr_host, TruePeakRec / tp_host, PcmRec / pcm_host,
-// LimitRec / lim_host, EdgesRec / edg_host).
+// LimitRec / lim_host, EdgesRec / edg_host, FilterOpts / fl_host).
 
 int64_t msg_sizeof(int32_t which) {
     switch (which) {
@@ -22,6 +22,7 @@ int64_t msg_sizeof(int32_t which) {
         case 8: return (int64_t)sizeof(msg_lrange_rec);
         case 9: return (int64_t)sizeof(msg_edges_rec);
         case 10: return (int64_t)sizeof(msg_edges_opts);
+        case 11: return (int64_t)sizeof(msg_filter_opts);
         default: return -1;
     }
 }
@@ -263,6 +264,26 @@ int msg_edges_host(float* x, int32_t channels, int64_t n, const msg_edges_opts* 
     EdgesRec r;
     edg_host(x, channels, n, edg_par(o), &r);
     std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The value checks msg_filter and msg_filter_host share
+static int fl_values(msg_ctx* ctx, const msg_filter_opts* opts, FilterOpts* o) {
+    static_assert(sizeof(FilterOpts) == sizeof(msg_filter_opts), "FilterOpts is msg_filter_opts");
+    static_assert(FL_MAX_SECTIONS == MSG_FILTER_MAX_SECTIONS && FL_REVERSE == MSG_FILTER_REVERSE, "the filter's limits and flag");
+    std::memcpy(o, opts, sizeof(*o));
+    if (const char* why = fl_refused(*o)) return fail(ctx, MSG_E_VALUE, why);
+    return MSG_OK;
+}
+
+// A biquad cascade over one signal in host memory, in place: the definition of filter.h as
+// one sequential float64 loop (fl_host)
+int msg_filter_host(float* x, int32_t channels, int64_t n, const msg_filter_opts* opts) {
+    if (!opts || n < 0 || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    FilterOpts o;
+    if (const int rc = fl_values(nullptr, opts, &o)) return rc;
+    fl_host(x, channels, n, o);
     return MSG_OK;
 }
 

@@ -29,6 +29,7 @@
 #include "pcm_shape.h"
 #include "limit.h"
 #include "edges.h"
+#include "filter.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -111,6 +112,9 @@ int msg_limit(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t
 }
 int msg_edges(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, const msg_edges_opts*, msg_edges_rec*,
               void*) {
+    return no_device();
+}
+int msg_filter(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, const msg_filter_opts*, void*) {
     return no_device();
 }
 #include "host_abi.inc"

@@ -241,3 +241,10 @@ hipError_t launch_limit(int n_sig, int channels, int os, unsigned env_tiles, uns
 struct EdgesPar;
 hipError_t launch_edges(int n_sig, int channels, unsigned find_tiles, unsigned apply_tiles, hipStream_t s, float* x,
                         const int64_t* meta, const EdgesPar& par, void* rec);
+
+// delivery filter (kernels_filter.h): the first sweep over tiles of FL_TILE frames writes every
+// full tile's zero-state end state, the scan turns them into incoming states, the second sweep
+// filters in place.  meta: offsets, frames, n_sig + 1 first tiles (fl_tiles); tab: fl_table of
+// the cascade; state: 2 * n_sections * channels doubles per tile; reverse: from the last frame
+hipError_t launch_filter(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
+                         int n_sections, int reverse, const double* tab, double* state);

@@ -40,6 +40,7 @@
 #include "pcm_shape.h"
 #include "limit.h"
 #include "edges.h"
+#include "filter.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"

@@ -1,7 +1,7 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
 // msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_quantize_shaped, msg_limit,
-// msg_edges.
+// msg_edges, msg_filter.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -413,5 +413,31 @@ int msg_edges(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offse
     if (const int rc = c.open(ctx->edg_meta)) return rc;
     HIPCHK(ctx, launch_edges(n_signals, channels, (unsigned)c.tiles, (unsigned)apply_tiles, c.s, x_dev, ctx->edg_meta.p,
                              par, rec_dev));
+    return c.finish();
+}
+
+int msg_filter(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n, int32_t n_signals,
+               const msg_filter_opts* opts, void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && opts, n_signals, channels)) return rc;
+    FilterOpts o;
+    if (const int rc = fl_values(ctx, opts, &o)) return rc;
+    if (const int rc = sig_aligned(ctx, channels, x_dev)) return rc;
+    if (n_signals == 0) return MSG_OK;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, fl_tiles, "signal", "filter")) return rc;
+    if (c.tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    // the pass writes where it reads: two signals sharing a frame would filter each other's output
+    SigRanges ranges;
+    for (int i = 0; i < n_signals; ++i)
+        if (n[i] > 0) ranges.emplace_back(offsets[i], offsets[i] + n[i]);
+    if (const int rc = sig_disjoint(ctx, ranges, "signal")) return rc;
+    if (c.tiles == 0) return MSG_OK;
+    std::vector<double> tab(FL_TAB_N);
+    fl_table(o, tab.data());
+    if (const int rc = c.open(ctx->fl_meta)) return rc;
+    HIPCHK(ctx, ctx->fl_state.ensure(c.parts() * 2 * o.n_sections * channels));
+    if (const int rc = c.upload(ctx->fl_tab, tab)) return rc;
+    HIPCHK(ctx, launch_filter(n_signals, channels, (unsigned)c.tiles, c.s, x_dev, ctx->fl_meta.p, o.n_sections,
+                              o.flags & FL_REVERSE, ctx->fl_tab.p, ctx->fl_state.p));
     return c.finish();
 }

@@ -20,6 +20,8 @@ from . import pcm as _pcm  # noqa: F401
 from . import limit as _limit  # noqa: F401
 from . import edges as _edges  # noqa: F401
 from .edges import Edges  # noqa: F401
+from . import filter as _filter  # noqa: F401
+from .filter import Filter  # noqa: F401
 
 
 def render(params, progress=None, device: int = 0):
@@ -29,7 +31,7 @@ def render(params, progress=None, device: int = 0):
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
                  out_lufs=None, out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf",
-                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None, out_edges=None):
+                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None, out_filter=None, out_edges=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -54,11 +56,14 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     dbtp, frames, rate; lrange.py; one device only, "audio" or "device").  ``out_shape``: with
     ``out_bits``, noise-shaped dither: "e3", "lipshitz5" or "f9" (pcm.py).  ``out_edges``: an
     edges.Edges, every render trimmed to the span that holds sound, faded, or looped before the
-    level rules (edges.py; one device only)."""
+    level rules (edges.py; one device only).  ``out_filter``: a filter.Filter, every render run
+    through its biquad cascade (a rumble high-pass, shelves, peaks, a low-pass) after the resampler
+    and before the edges and the level rules, which then see what is delivered (filter.py; one
+    device only)."""
     if devices is not None and len(list(devices)) > 1:
         from .export import Delivery
         Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak, bits=out_bits,
-                 limiter=out_limiter, report=out_report, edges=out_edges).one_device(
+                 limiter=out_limiter, report=out_report, edges=out_edges, filter=out_filter).one_device(
             "out_", len(list(devices)), companions=True)
         # an option of out_bits and no rule of one_device's: with out_bits it was refused above
         if out_shape is not None:
@@ -71,7 +76,7 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     return _rb(params_list, device, results, out_sr=out_sr, out_peak=out_peak, out_lufs=out_lufs,
                out_ceiling=out_ceiling, out_true_peak=out_true_peak, out_bits=out_bits, out_dither=out_dither,
                out_dither_seed=out_dither_seed, out_limiter=out_limiter, out_report=out_report, out_shape=out_shape,
-               out_edges=out_edges)
+               out_edges=out_edges, out_filter=out_filter)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):
@@ -152,6 +157,14 @@ def edges(x, sr, edges, device: int = 0):
     return _edges.edges(x, sr, edges, device)
 
 
+def filter(x, sr, flt, device: int = 0, reverse=False):
+    """Run x, (n,) or (n, 2), at sr Hz through the biquad cascade of a filter.Filter on the device
+    (see filter.py): high- and low-pass, shelves, peaks or raw sections, in float64, optionally
+    zero-phase.  NumPy in: a filtered float32 copy out; a device tensor in: filtered in place with
+    no host synchronise and returned."""
+    return _filter.filter(x, sr, flt, device, reverse)
+
+
 def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0, shape=None):
     """x, (n,) or (n, 2) float32, as 16- or 24-bit PCM quantised on the device with TPDF
     dither (or "none") from the stream (seed, key); see pcm.py.  NumPy in, int16 (or
@@ -169,6 +182,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     ceiling in dBTP, ``export_bits`` as 16- or 24-bit PCM with TPDF dither (``export_shape``: noise-shaped), ``export_limiter`` holding
     that ceiling with the look-ahead limiter, ``export_report`` with the EBU R 128 meters of every
     delivered variant in a list and, with a folder, in loudness_report.csv, ``export_edges`` trimming,
-    fading or looping every variant's ends (one device)."""
+    fading or looping every variant's ends, ``export_filter`` running every variant through a
+    filter.Filter before them (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

@@ -120,6 +120,10 @@ class MsgEdgesOpts(C.Structure):
                [(k, C.c_int64) for k in ("pre", "post", "fade_in", "fade_out", "loop")]
 
 
+class MsgFilterOpts(C.Structure):
+    _fields_ = [("n_sections", C.c_int32), ("flags", C.c_int32), ("sos", (C.c_double * 6) * 8)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -190,6 +194,9 @@ _PROTOS = {
     "msg_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                             C.POINTER(MsgEdgesOpts), C.c_void_p, C.c_void_p]),
     "msg_edges_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(MsgEdgesOpts), C.c_void_p]),
+    "msg_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                             C.POINTER(MsgFilterOpts), C.c_void_p]),
+    "msg_filter_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(MsgFilterOpts)]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
@@ -228,7 +235,7 @@ def lib() -> C.CDLL:
                 raise RuntimeError("libmsgpu ABI version mismatch")
             for which, st in enumerate((MsgPreset, MsgEvent, MsgPlanInfo, MsgDigestRec, MsgLoudnessRec,
                                         MsgTruePeakRec, MsgPcmRec, MsgLimitRec, MsgLRangeRec, MsgEdgesRec,
-                                        MsgEdgesOpts)):
+                                        MsgEdgesOpts, MsgFilterOpts)):
                 if L.msg_sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmsgpu struct {st.__name__} size mismatch: "
                                        f"{L.msg_sizeof(which)} != {C.sizeof(st)}")

@@ -132,7 +132,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
                       export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
                       export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None,
-                      export_report=None, export_shape=None, export_edges=None):
+                      export_report=None, export_shape=None, export_filter=None, export_edges=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -192,6 +192,11 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     as a seamless loop (``loop_ms``).  The files, the returned audio, the report's ``frames`` and
     ``loudness_report.csv`` carry the delivered span; the meters and the ceiling hold on it, and
     the dither counts from its first word.  One device only.
+
+    ``export_filter``: a filter.Filter: every variant is run through its biquad cascade (a rumble
+    high-pass, shelves, peaks, a low-pass, or raw sections; ``zero_phase`` for no phase shift) in
+    float64 in HBM, after the resampler and before ``export_edges`` and the level rules, so the
+    meters, the ceiling and the trim see what is delivered (filter.py).  One device only.
     """
     from .pack import PackedBatch, out_frames
 
@@ -200,7 +205,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     delivery = Delivery(sr=export_sr, peak=export_peak, lufs=export_lufs, ceiling=export_ceiling,
                         true_peak=export_true_peak, bits=export_bits, dither=export_dither,
                         dither_seed=export_dither_seed, limiter=export_limiter, report=export_report,
-                        shape=export_shape, edges=export_edges)
+                        shape=export_shape, edges=export_edges, filter=export_filter)
     delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False,
                    rates=[merged(base_params)["base_sr"]])
     first_row = len(export_report) if export_report is not None else 0

@@ -26,7 +26,7 @@ import numpy as np
 
 from .engine import default_engine
 from .export import (Delivery, deliver, unpack_all,  # noqa: F401  (the packed passes stay importable from here)
-                     edges_packed, limiter_packed, loudness_packed, quantize_packed, resample_packed, truepeak_packed)
+                     edges_packed, filter_packed, limiter_packed, loudness_packed, quantize_packed, resample_packed, truepeak_packed)
 from .pack import PackedBatch, design_sr
 from .params import first_missing_key, merged
 
@@ -94,7 +94,7 @@ def _out_peaks(params_list, out_peak):
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
                  out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
-                 out_limiter=None, out_report=None, out_shape=None, out_edges=None):
+                 out_limiter=None, out_report=None, out_shape=None, out_filter=None, out_edges=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -121,10 +121,14 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     edges.Edges, the ends of every render shaped after the resampler and before the level rules
     (export.edges_packed): trimmed to the span that holds sound, faded in and out, or its tail
     crossfaded into its head as a loop.  The arrays, tensors, reports and dither streams are then
-    those of the span; a trim or a loop costs the chain one host wait for the spans."""
+    those of the span; a trim or a loop costs the chain one host wait for the spans.  ``out_filter``: a
+    filter.Filter, every render run through its biquad cascade in float64 where it lies
+    (export.filter_packed), after the resampler and before the edges and the level rules: a trim sees
+    the filtered signal, fades still end at zero, and loudness, true peak, limiter and report
+    measure what is delivered."""
     delivery = Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak,
                         bits=out_bits, dither=out_dither, dither_seed=out_dither_seed, limiter=out_limiter,
-                        report=out_report, shape=out_shape, edges=out_edges)
+                        report=out_report, shape=out_shape, edges=out_edges, filter=out_filter)
     params_list = list(params_list)
     delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)

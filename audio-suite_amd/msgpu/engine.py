@@ -369,6 +369,20 @@ class Engine:
                           stream=stream)
         return rec
 
+    def filter(self, x, offsets, lens, channels, sr, flt, reverse=False, stream=None):
+        """msg_filter: the biquad cascade of a filter.Filter designed at ``sr`` Hz over signals lying
+        in a device float32 tensor (as Engine.true_peak), in place.  ``zero_phase`` filters make the
+        forward call and then the reverse call with the same cascade; otherwise ``reverse`` runs the
+        one call from each signal's last frame to its first.  Returns x; enqueued on ``stream``, no
+        host synchronise."""
+        from .filter import _opts
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        sos = flt.design(sr)
+        for rev in ((False, True) if flt.zero_phase else (bool(reverse),)):
+            opts = _opts(sos, rev)
+            self._signal_call(L.lib().msg_filter, x, channels, off, cnt, C.byref(opts), stream=stream)
+        return x
+
     def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None,
                  shape=None):
         """msg_quantize of signals lying in a device float32 tensor (as Engine.true_peak):

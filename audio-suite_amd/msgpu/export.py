@@ -1,15 +1,17 @@
-"""The delivery chain of a rendered batch: resample -> edges -> level -> report -> quantise, in HBM.
+"""The delivery chain of a rendered batch: resample -> filter -> edges -> level -> report -> quantise, in HBM.
 
 ``render_batch`` (dropin.py, ``out_*`` options) and ``render_variations`` (batch.py,
 ``export_*`` options) describe what they deliver with one ``Delivery``, check it with
 ``Delivery.check`` and run it with ``deliver``; each pass works on the renders where
-they lie (resample.py, edges.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing
+they lie (resample.py, filter.py, edges.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing
 here synchronises, with one exception: an ``edges`` rule with a trim or a loop crossfade changes what
 is delivered of each render, so ``deliver`` reads the spans the device found (8 int64 per render)
 before it sizes the later passes.  That is the chain's one host wait; fades alone wait for nothing.
 A new export rule is a field of ``Delivery`` (after the last one, so the positional order stays),
 its row in ``RULES``, its lines in ``check`` and its step in ``deliver``; a pass that runs at the
-renders' rates is a closure handed to ``per_rate``.
+renders' rates is a closure handed to ``per_rate``.  The twelve dataclass fields and their order
+are pinned by the earlier rules' tests, so ``filter``, the rule after ``edges``, is a keyword of
+``Delivery`` and no dataclass field: ``Delivery(filter=f)``, seen by ``==`` and ``repr``.
 """
 from __future__ import annotations
 
@@ -21,16 +23,16 @@ import numpy as np
 REPORT_DTYPE = np.dtype([(k, "<f8") for k in ("lufs", "lra", "lo", "hi", "max_momentary", "max_short", "peak",
                                               "true_peak", "dbtp")] + [("frames", "<i8"), ("rate", "<i8")])
 
-# The rules, each a field of Delivery: (the rule, the option that comes with it, why it works on one
+# The rules, each a field of Delivery (``filter``: its keyword): (the rule, the option that comes with it, why it works on one
 # device only, whether results "stats" may ask for it).  ``dither``, ``dither_seed`` and ``shape`` are
 # options of ``bits`` that ask for nothing alone, so they have no row.
 RULES = (("sr", "peak", " (multi.py sizes its shared memory by out_n)", False), ("lufs", "ceiling", "", False),
          ("true_peak", None, "", False), ("bits", None, "", False), ("limiter", None, "", False),
-         ("report", None, "", False), ("edges", None, "", False))
+         ("report", None, "", False), ("edges", None, "", False), ("filter", None, "", False))
 
 
 @dataclass
-class Delivery:
+class DeliveryFields:
     sr: object = None             # deliver at this rate (None: as rendered)
     peak: object = None           # the peak resampled renders are rescaled to: None, "preset" or a number
     lufs: object = None           # BS.1770 integrated loudness to deliver at
@@ -136,16 +138,50 @@ class Delivery:
             except ValueError as e:
                 raise ValueError(f"{p}edges: {e}") from None
         self.one_device(p, n_devices, ("edges",))
+        if self.filter is not None:
+            from .filter import Filter
+            if not isinstance(self.filter, Filter):
+                raise ValueError(f"{p}filter must be None or a Filter")
+            try:
+                self.filter.check()
+                for rate in ([self.sr] if self.sr is not None else rates):
+                    self.filter.check(rate)
+            except ValueError as e:
+                raise ValueError(f"{p}filter: {e}") from None
+        self.one_device(p, n_devices, ("filter",))
         if results == "stats":
             for rule, _, _, with_stats in RULES:
                 if not with_stats and getattr(self, rule) is not None:
                     raise ValueError(f"{p}{rule} applies to results 'audio' or 'device'")
 
 
+class Delivery(DeliveryFields):
+    """What a front end delivers: DeliveryFields' rules, given as they always were, and after them
+    ``filter``, a filter.Filter whose biquad cascade runs in front of the edges and the level rules.
+    It is given by keyword only and is not a dataclass field (``dataclasses.fields`` and
+    ``dataclasses.replace`` do not see it; ``==`` and ``repr`` do)."""
+    filter = None
+
+    def __init__(self, *args, filter=None, **kw):
+        super().__init__(*args, **kw)
+        self.filter = filter
+
+    def __eq__(self, other):
+        same = DeliveryFields.__eq__(self, other)
+        return same if same is NotImplemented else same and self.filter == other.filter
+
+    __hash__ = None
+
+    def __repr__(self):
+        return DeliveryFields.__repr__(self)[:-1] + f", filter={self.filter!r})"
+
+
 def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     """Run ``delivery`` over renders lying in a device tensor ((frames, 2) float32, render i
     at frame offsets[i] with lens[i] frames at rates[i] Hz): resampled to ``delivery.sr``
-    (``peaks``: resample_packed's), its ends shaped by ``delivery.edges`` (edges_packed; from there
+    (``peaks``: resample_packed's), filtered by ``delivery.filter`` (filter_packed: in front of the edges, so
+    that a trim sees the filtered signal and the fades still end at zero, and in front of the level rules, so
+    that loudness, true peak, limiter and report measure what is delivered), its ends shaped by ``delivery.edges`` (edges_packed; from there
     on a render is the span that rule left of it), levelled at the rate delivered, metered as delivered when
     ``delivery.report`` is a list (report_packed; ``delivery.flush_report`` reads the rows once
     the caller has waited for its copy), quantised with the dither streams
@@ -158,6 +194,8 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     if d.sr is not None:
         out, offsets, lens = resample_packed(eng, out, offsets, lens, rates, int(d.sr), peaks)
         rates = [int(d.sr)] * len(lens)
+    if d.filter is not None:
+        filter_packed(eng, out, offsets, lens, rates, d.filter)
     if d.edges is not None:
         offsets, lens, _ = edges_packed(eng, out, offsets, lens, rates, d.edges)
     _level(eng, out, offsets, lens, rates, d.lufs, d.ceiling, d.true_peak, d.limiter_ms())
@@ -252,6 +290,17 @@ def edges_packed(eng, y, offsets, lens, rates, edges):
         return offsets, lens, rec
     spans = records(rec)
     return offsets + spans["start"], spans["end"] - spans["start"], rec
+
+
+def filter_packed(eng, y, offsets, lens, rates, flt):
+    """Run renders lying in a device tensor ((frames, 2) float32, render i at frame offsets[i] with
+    lens[i] frames at rates[i] Hz) through the cascade of ``flt``, a filter.Filter, where they lie:
+    msg_filter per distinct rate (the design depends on the rate), twice for a zero-phase filter.
+    Nothing is moved and there is no record; no host synchronise."""
+    def run(off, cnt, rate):
+        eng.filter(y, off, cnt, 2, rate, flt)
+        return ()
+    per_rate(eng, y, offsets, lens, rates, run, ())
 
 
 def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None, true_peak=None):

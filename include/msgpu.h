@@ -122,7 +122,7 @@ int         msg_abi_version(void);
 int         msg_host_threads(void);
 /* sizeof of the ABI structs (0 msg_preset, 1 msg_event, 2 msg_plan_info, 3 msg_digest_rec,
  * 4 msg_loudness_rec, 5 msg_truepeak_rec, 6 msg_pcm_rec, 7 msg_limit_rec, 8 msg_lrange_rec,
- * 9 msg_edges_rec, 10 msg_edges_opts) for binding checks */
+ * 9 msg_edges_rec, 10 msg_edges_opts, 11 msg_filter_opts) for binding checks */
 int64_t     msg_sizeof(int32_t which);
 msg_ctx*    msg_create(int device_ordinal);
 void        msg_destroy(msg_ctx* ctx);
@@ -527,6 +527,36 @@ int msg_edges(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offse
 /* The same definition as one loop over one signal in host memory, in place (x: n frames of
  * `channels` interleaved words); needs no device. */
 int msg_edges_host(float* x, int32_t channels, int64_t n, const msg_edges_opts* opts, msg_edges_rec* rec);
+
+/* A biquad cascade over signals lying in HBM, in place (csrc/filter.h holds the definition,
+ * DESIGN.md 4j the kernels).  The cascade is n_sections (1 .. MSG_FILTER_MAX_SECTIONS)
+ * second-order sections in scipy's row layout b0 b1 b2 a0 a1 a2, float64, a0 == 1.  Each
+ * section runs in transposed direct form II in float64, two state words per channel,
+ *   y = b0 x + z0,  z0 = (b1 x - a1 y) + z1,  z1 = b2 x - a2 y
+ * (no contraction); sections run in series, channels are independent, a signal starts from
+ * zero state at its own first frame, and the cascade's float64 output is rounded once to
+ * float32 and replaces the input.  flags = MSG_FILTER_REVERSE runs the same recurrence from
+ * the last frame to the first; forward then reverse with one cascade is a zero-phase filter
+ * with twice every band's gain in dB.  The device differs from msg_filter_host by float64
+ * roundings only (far below the one float32 rounding); a signal's samples are the same bits
+ * from run to run, alone or in any batch.  A NaN or an infinity spoils only its own signal
+ * and channel, from its frame on in the direction of the run. */
+enum { MSG_FILTER_MAX_SECTIONS = 8 };
+enum msg_filter_flag { MSG_FILTER_REVERSE = 1 };
+typedef struct msg_filter_opts {
+    int32_t n_sections, flags;
+    double sos[8][6];
+} msg_filter_opts;
+/* Signals as for msg_edges, which must not overlap (MSG_E_VALUE).  A section count out of
+ * range, a coefficient that is not finite, a0 != 1, flags other than 0 or MSG_FILTER_REVERSE,
+ * or a section outside the stability triangle (|a2| < 1, |a1| < 1 + a2): MSG_E_VALUE.  Two
+ * sweeps over the samples and a scan over tiles between them enqueue back to back on stream
+ * with no host synchronise; one call in flight per context. */
+int msg_filter(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+               int32_t n_signals, const msg_filter_opts* opts, void* stream);
+/* The same definition as one sequential loop over one signal in host memory, in place (x: n
+ * frames of `channels` interleaved words); needs no device. */
+int msg_filter_host(float* x, int32_t channels, int64_t n, const msg_filter_opts* opts);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
