@@ -391,6 +391,9 @@ struct msg_ctx {
     // msg_filter: signal extents + tile bases, the cascade's table (filter.h), per-tile states
     DevBuf<int64_t> fl_meta;
     DevBuf<double> fl_tab, fl_state;
+    // msg_stereo_meter / msg_stereo: signal extents + tile bases (+ the fold's output offsets), per-tile sums
+    DevBuf<int64_t> img_meta;
+    DevBuf<double> img_part;
 
     // What must come first and in this order; the members' destructors follow.
     ~msg_ctx() {

@@ -2,12 +2,13 @@
 // sizes (msg_sizeof), the render plan (plan.h), the NumPy stream primitives (nprng.h) and
 // the host references of the render digest (digest.h), of the loudness and true-peak
 // measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantisers (pcm.h, pcm_shape.h) and of the look-ahead
-// limiter (limit.h), of the edges pass (edges.h) and of the delivery filter (filter.h).  Included
+// limiter (limit.h), of the edges pass (edges.h), of the delivery filter (filter.h) and of the stereo
+// meter and image (image.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
 // named above (DigestPart / dg_host, LoudRec / ld_host, LRangeRec / lr_host, TruePeakRec / tp_host, PcmRec / pcm_host,
-// LimitRec / lim_host, EdgesRec / edg_host, FilterOpts / fl_host).
+// LimitRec / lim_host, EdgesRec / edg_host, FilterOpts / fl_host, ImageRec / img_meter_host / img_host).
 
 int64_t msg_sizeof(int32_t which) {
     switch (which) {
@@ -284,6 +285,45 @@ int msg_filter_host(float* x, int32_t channels, int64_t n, const msg_filter_opts
     FilterOpts o;
     if (const int rc = fl_values(nullptr, opts, &o)) return rc;
     fl_host(x, channels, n, o);
+    return MSG_OK;
+}
+
+// The stereo meter over one signal in host memory: the definition of image.h as one sequential
+// float64 loop (img_meter_host)
+int msg_stereo_meter_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_stereo_rec* rec) {
+    static_assert(sizeof(ImageRec) == sizeof(msg_stereo_rec), "ImageRec is msg_stereo_rec");
+    if (!rec || n < 0 || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 2");
+    if (!img_rate_ok(sr)) return fail(nullptr, MSG_E_VALUE, "the sample rate must be a multiple of 10, at least 4000");
+    ImageRec r;
+    img_meter_host(x, n, sr, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The value checks msg_stereo and msg_stereo_host share: a finite matrix, or a finite fold row
+static int img_values(msg_ctx* ctx, const float* matrix, const float* fold) {
+    const float* v = fold ? fold : matrix;
+    for (int i = 0; i < (fold ? 2 : 4); ++i)
+        if (!std::isfinite(v[i])) return fail(ctx, MSG_E_VALUE, "the matrix must be finite");
+    return MSG_OK;
+}
+
+// The stereo image over one signal in host memory (img_host): the matrix in place, or, fold not
+// null, the fold row into y (n floats, no overlap with x), x unchanged.  rec: null, or a meter
+// record whose corr < 0 inverts the right channel first.
+int msg_stereo_host(float* x, int32_t channels, int64_t n, const float* matrix, const float* fold, float* y,
+                    const msg_stereo_rec* rec) {
+    if ((!matrix && !fold) || n < 0 || (n > 0 && (!x || (fold && !y)))) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 2");
+    if (const int rc = img_values(nullptr, matrix, fold)) return rc;
+    if (fold && n > 0) {
+        const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
+        if (x0 < y0 + (uintptr_t)n * 4 && y0 < x0 + (uintptr_t)n * 8) return fail(nullptr, MSG_E_VALUE, "output ranges overlap");
+    }
+    const bool flip = rec && rec->corr < 0.0;
+    if (!fold && !flip && img_identity(matrix)) return MSG_OK;     // the identity touches nothing
+    img_host(x, n, matrix, fold, y, flip);
     return MSG_OK;
 }
 

@@ -4,7 +4,8 @@
 // the host references of the render digest (digest.h, msg_digest_host) and of the
 // loudness and true-peak measurements (loudness.h, msg_loudness_host; truepeak.h,
 // msg_truepeak_host), of the PCM quantiser (pcm.h, msg_quantize_host) and of the
-// look-ahead limiter (limit.h, msg_limit_host) and of the edges pass (edges.h, msg_edges_host),
+// look-ahead limiter (limit.h, msg_limit_host), of the edges pass (edges.h, msg_edges_host) and of the
+// stereo meter and image (image.h, msg_stereo_meter_host, msg_stereo_host),
 // compiled by g++ with -fsanitize=address,undefined into
 // msgpu/libmsgpu_hostsan.so.  The device entry points are stubs that fail with
 // MSG_E_DEVICE, so the ctypes binding (_lib.py) loads this library unchanged
@@ -30,6 +31,7 @@
 #include "limit.h"
 #include "edges.h"
 #include "filter.h"
+#include "image.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -115,6 +117,14 @@ int msg_edges(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t
     return no_device();
 }
 int msg_filter(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, const msg_filter_opts*, void*) {
+    return no_device();
+}
+int msg_stereo_meter(msg_ctx*, const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, msg_stereo_rec*,
+                     void*) {
+    return no_device();
+}
+int msg_stereo(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, const float*, const float*, float*,
+               const int64_t*, const msg_stereo_rec*, void*) {
     return no_device();
 }
 #include "host_abi.inc"

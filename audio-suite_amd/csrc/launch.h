@@ -248,3 +248,15 @@ hipError_t launch_edges(int n_sig, int channels, unsigned find_tiles, unsigned a
 // the cascade; state: 2 * n_sections * channels doubles per tile; reverse: from the last frame
 hipError_t launch_filter(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
                          int n_sections, int reverse, const double* tab, double* state);
+
+// stereo meter (kernels_image.h): one sweep over tiles of IMG_TILE frames that never straddle a
+// hop writes three float64 sums per tile, then one wave per signal folds them into the record.
+// meta: offsets, frames, n_sig + 1 first tiles (img_tiles); part: 3 doubles per tile; rec:
+// msg_stereo_rec records
+hipError_t launch_image_meter(int n_sig, unsigned tiles, hipStream_t s, const float* x, const int64_t* meta, int64_t hop,
+                              double* part, void* rec);
+// stereo image: the 2 x 2 matrix m in place, or (fold not null) the fold row into y at the output
+// offsets that follow the first tiles in meta (img_apply_tiles); rec: null, or the meter's
+// records, whose corr < 0 inverts the right channel of that signal first
+hipError_t launch_image_apply(int n_sig, unsigned tiles, hipStream_t s, float* x, const int64_t* meta, const float* m,
+                              const float* fold, float* y, const void* rec);

@@ -41,6 +41,7 @@
 #include "limit.h"
 #include "edges.h"
 #include "filter.h"
+#include "image.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"

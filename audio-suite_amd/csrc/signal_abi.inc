@@ -1,7 +1,7 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
 // msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_quantize_shaped, msg_limit,
-// msg_edges, msg_filter.
+// msg_edges, msg_filter, msg_stereo_meter, msg_stereo.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -439,5 +439,56 @@ int msg_filter(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offs
     if (const int rc = c.upload(ctx->fl_tab, tab)) return rc;
     HIPCHK(ctx, launch_filter(n_signals, channels, (unsigned)c.tiles, c.s, x_dev, ctx->fl_meta.p, o.n_sections,
                               o.flags & FL_REVERSE, ctx->fl_tab.p, ctx->fl_state.p));
+    return c.finish();
+}
+
+int msg_stereo_meter(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                     int32_t n_signals, int32_t sr, msg_stereo_rec* rec_dev, void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && rec_dev, n_signals, channels)) return rc;
+    if (channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 2");
+    if (!img_rate_ok(sr)) return fail(ctx, MSG_E_VALUE, "the sample rate must be a multiple of 10, at least 4000");
+    if (const int rc = sig_aligned(ctx, channels, x_dev)) return rc;
+    if (n_signals == 0) return MSG_OK;
+    const int64_t hop = sr / 10;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, [hop](int64_t f) { return img_tiles(f, hop); }, "signal", "meter"))
+        return rc;
+    if (c.tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    if (const int rc = c.open(ctx->img_meta)) return rc;
+    HIPCHK(ctx, ctx->img_part.ensure(c.parts() * 3));
+    HIPCHK(ctx, launch_image_meter(n_signals, (unsigned)c.tiles, c.s, x_dev, ctx->img_meta.p, hop, ctx->img_part.p, rec_dev));
+    return c.finish();
+}
+
+int msg_stereo(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n, int32_t n_signals,
+               const float* matrix, const float* fold, float* y_dev, const int64_t* out_offsets,
+               const msg_stereo_rec* rec_dev, void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && (matrix || fold) && (!fold || out_offsets), n_signals, channels))
+        return rc;
+    if (channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 2");
+    if (const int rc = img_values(ctx, matrix, fold)) return rc;
+    if (const int rc = sig_aligned(ctx, channels, x_dev)) return rc;
+    if (fold && (reinterpret_cast<uintptr_t>(y_dev) & 3)) return fail(ctx, MSG_E_ARG, "the output must be 4-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, img_apply_tiles, "signal", "image", fold ? (size_t)n_signals : 0))
+        return rc;
+    if (c.tiles > 0 && (!x_dev || (fold && !y_dev))) return fail(ctx, MSG_E_ARG, "null buffer");
+    // in place the pass writes where it reads; folded, no output may lie on an input or on another output
+    SigRanges ranges;
+    const int64_t xb = (int64_t)reinterpret_cast<uintptr_t>(x_dev), yb = (int64_t)reinterpret_cast<uintptr_t>(y_dev);
+    for (int i = 0; i < n_signals; ++i) {
+        if (fold) {
+            if (out_offsets[i] < 0) return fail(ctx, MSG_E_ARG, "bad output offset");
+            c.extra_row(n_signals, 0)[i] = out_offsets[i];
+        }
+        if (n[i] == 0) continue;
+        ranges.emplace_back(xb + offsets[i] * 8, xb + (offsets[i] + n[i]) * 8);
+        if (fold) ranges.emplace_back(yb + out_offsets[i] * 4, yb + (out_offsets[i] + n[i]) * 4);
+    }
+    if (const int rc = sig_disjoint(ctx, ranges, "signal")) return rc;
+    if (c.tiles == 0 || (!fold && !rec_dev && img_identity(matrix))) return MSG_OK;   // the identity launches nothing
+    if (const int rc = c.open(ctx->img_meta)) return rc;
+    HIPCHK(ctx, launch_image_apply(n_signals, (unsigned)c.tiles, c.s, x_dev, ctx->img_meta.p, matrix, fold, y_dev, rec_dev));
     return c.finish();
 }

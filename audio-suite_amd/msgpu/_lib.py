@@ -124,6 +124,11 @@ class MsgFilterOpts(C.Structure):
     _fields_ = [("n_sections", C.c_int32), ("flags", C.c_int32), ("sos", (C.c_double * 6) * 8)]
 
 
+class MsgStereoRec(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("sll", "srr", "slr", "corr", "corr_min", "corr_min_block", "blocks_kept",
+                                          "blocks")]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -197,6 +202,12 @@ _PROTOS = {
     "msg_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                              C.POINTER(MsgFilterOpts), C.c_void_p]),
     "msg_filter_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(MsgFilterOpts)]),
+    "msg_stereo_meter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                                   C.c_int32, C.c_void_p, C.c_void_p]),
+    "msg_stereo_meter_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "msg_stereo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    "msg_stereo_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),

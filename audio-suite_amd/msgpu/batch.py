@@ -132,7 +132,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
                       export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
                       export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None,
-                      export_report=None, export_shape=None, export_filter=None, export_edges=None):
+                      export_report=None, export_shape=None, export_stereo=None, export_filter=None, export_edges=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -197,6 +197,13 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     high-pass, shelves, peaks, a low-pass, or raw sections; ``zero_phase`` for no phase shift) in
     float64 in HBM, after the resampler and before ``export_edges`` and the level rules, so the
     meters, the ceiling and the trim see what is delivered (filter.py).  One device only.
+
+    ``export_stereo``: a stereo.Stereo: every variant is metered for phase correlation (``meter``: a
+    list that gets one row per variant), given a width, balance, swap or polarity matrix
+    (``invert="auto"``: the right channel inverted where the correlation is negative) or folded to
+    mono (``channels=1``) in HBM, after ``export_filter`` and before ``export_edges`` and the level
+    rules, which then level, hold and report the mono render; the files are then one-channel WAVs
+    and the returned audio is (n, 1) (stereo.py).  One device only.
     """
     from .pack import PackedBatch, out_frames
 
@@ -205,7 +212,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     delivery = Delivery(sr=export_sr, peak=export_peak, lufs=export_lufs, ceiling=export_ceiling,
                         true_peak=export_true_peak, bits=export_bits, dither=export_dither,
                         dither_seed=export_dither_seed, limiter=export_limiter, report=export_report,
-                        shape=export_shape, edges=export_edges, filter=export_filter)
+                        shape=export_shape, edges=export_edges, filter=export_filter, stereo=export_stereo)
     delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False,
                    rates=[merged(base_params)["base_sr"]])
     first_row = len(export_report) if export_report is not None else 0
@@ -254,7 +261,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
         if export_bits is not None:
             if export_records is not None:
                 export_records.extend(records(rec))
-            audio = unpack_all(host, offsets, lens, export_bits)
+            audio = unpack_all(host, offsets, lens, export_bits, delivery.channels())
         else:
             audio = [host[int(off):int(off) + int(n)].copy() for off, n in zip(offsets, lens)]
         for key, a in zip(chunk, audio):

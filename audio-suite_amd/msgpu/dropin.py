@@ -26,7 +26,8 @@ import numpy as np
 
 from .engine import default_engine
 from .export import (Delivery, deliver, unpack_all,  # noqa: F401  (the packed passes stay importable from here)
-                     edges_packed, filter_packed, limiter_packed, loudness_packed, quantize_packed, resample_packed, truepeak_packed)
+                     edges_packed, filter_packed, limiter_packed, loudness_packed, quantize_packed, resample_packed,
+                     stereo_packed, truepeak_packed)
 from .pack import PackedBatch, design_sr
 from .params import first_missing_key, merged
 
@@ -94,7 +95,7 @@ def _out_peaks(params_list, out_peak):
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
                  out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
-                 out_limiter=None, out_report=None, out_shape=None, out_filter=None, out_edges=None):
+                 out_limiter=None, out_report=None, out_shape=None, out_stereo=None, out_filter=None, out_edges=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -125,10 +126,15 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     filter.Filter, every render run through its biquad cascade in float64 where it lies
     (export.filter_packed), after the resampler and before the edges and the level rules: a trim sees
     the filtered signal, fades still end at zero, and loudness, true peak, limiter and report
-    measure what is delivered."""
+    measure what is delivered.  ``out_stereo``: a stereo.Stereo (export.stereo_packed), after the filter
+    and before the edges and the level rules: a phase-correlation meter (``meter``: a list that gets
+    one row per render, read with the report's rows), a width, balance, swap or polarity matrix over
+    every frame (``invert="auto"`` repairs the renders whose correlation is negative, on the device),
+    and ``channels=1``, the fold to mono in HBM, after which every later rule, the report and the
+    quantiser work on the mono render and the arrays and tensors are (n, 1)."""
     delivery = Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak,
                         bits=out_bits, dither=out_dither, dither_seed=out_dither_seed, limiter=out_limiter,
-                        report=out_report, shape=out_shape, edges=out_edges, filter=out_filter)
+                        report=out_report, shape=out_shape, edges=out_edges, filter=out_filter, stereo=out_stereo)
     params_list = list(params_list)
     delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)
@@ -147,5 +153,5 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
         return device_stats(eng, out, packed.offsets, packed.out_n)
     host = y.cpu().numpy()                       # quantised: the bytes cross, not the float32 renders
     if out_bits is not None:
-        return unpack_all(host, off, lens, out_bits)
+        return unpack_all(host, off, lens, out_bits, delivery.channels())
     return [host[int(o):int(o) + int(n)].copy() for o, n in zip(off, lens)]

@@ -383,6 +383,54 @@ class Engine:
             self._signal_call(L.lib().msg_filter, x, channels, off, cnt, C.byref(opts), stream=stream)
         return x
 
+    def stereo_meter(self, x, offsets, lens, sr, stream=None):
+        """msg_stereo_meter of stereo signals lying in a device float32 tensor (interleaved L/R
+        frames, signal i at frame offsets[i] with lens[i] frames at sr Hz): the three float64 sums,
+        the correlation and the smallest 400 ms block correlation (stereo.py).  Returns the device
+        records, a float64 tensor (signals, 8) whose rows are msg_stereo_rec (stereo.records reads
+        them on the host); enqueued on ``stream``, no host synchronise."""
+        channels, off, cnt = self._signals(x, offsets, lens, 2)
+        sr = _check_rate(sr)
+        rec = self.torch.empty((int(off.size), 8), dtype=self.torch.float64, device=x.device)
+        if not off.size:                      # no signal: no record to point at
+            return rec
+        self._signal_call(L.lib().msg_stereo_meter, x, channels, off, cnt, sr, C.c_void_p(rec.data_ptr()), stream=stream)
+        return rec
+
+    def stereo(self, x, offsets, lens, stereo, rec=None, out=None, stream=None):
+        """msg_stereo: the 2 x 2 matrix of a stereo.Stereo over stereo signals lying in a device
+        float32 tensor (as Engine.stereo_meter), in place, or, ``stereo.channels == 1``, its fold row
+        into ``out`` (a float32 tensor that does not overlap x; a new (frames, 1) one when None), the
+        outputs packed back to back in signal order.  ``rec``: the signals' device records of
+        Engine.stereo_meter; a signal with corr < 0 then has its right channel inverted first, on the
+        device (``invert="auto"`` needs it).  Returns (x, offsets) or (out, out_offsets); the identity
+        launches nothing.  Enqueued on ``stream``, no host synchronise."""
+        torch = self.torch
+        channels, off, cnt = self._signals(x, offsets, lens, 2)
+        m, fold = stereo.matrix_at()
+        n = int(off.size)
+        if rec is not None and (rec.dtype != torch.float64 or not rec.is_contiguous() or rec.device != x.device or
+                                rec.numel() < 8 * n):
+            raise ValueError("rec must be the float64 record tensor of Engine.stereo_meter on x's device")
+        if stereo.invert == "auto" and rec is None:
+            raise ValueError("invert='auto' needs the records of Engine.stereo_meter")
+        m = np.ascontiguousarray(m.reshape(4))
+        rp = None if rec is None else C.c_void_p(rec.data_ptr())
+        if stereo.channels == 2:
+            self._signal_call(L.lib().msg_stereo, x, channels, off, cnt, m.ctypes.data_as(C.c_void_p), None, None, None,
+                              rp, stream=stream)
+            return x, off
+        out_off = (np.cumsum(cnt) - cnt).astype(np.int64)
+        total = int(cnt.sum())
+        if out is None:
+            out = torch.empty((total, 1), dtype=torch.float32, device=x.device)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device or out.numel() < total:
+            raise ValueError("out must be a contiguous float32 tensor on x's device with room for every output")
+        self._signal_call(L.lib().msg_stereo, x, channels, off, cnt, m.ctypes.data_as(C.c_void_p),
+                          fold.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()), out_off.ctypes.data_as(_I64P), rp,
+                          stream=stream)
+        return out, out_off
+
     def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None,
                  shape=None):
         """msg_quantize of signals lying in a device float32 tensor (as Engine.true_peak):

@@ -1,9 +1,9 @@
-"""The delivery chain of a rendered batch: resample -> filter -> edges -> level -> report -> quantise, in HBM.
+"""The delivery chain of a rendered batch: resample -> filter -> stereo -> edges -> level -> report -> quantise, in HBM.
 
 ``render_batch`` (dropin.py, ``out_*`` options) and ``render_variations`` (batch.py,
 ``export_*`` options) describe what they deliver with one ``Delivery``, check it with
 ``Delivery.check`` and run it with ``deliver``; each pass works on the renders where
-they lie (resample.py, filter.py, edges.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing
+they lie (resample.py, filter.py, stereo.py, edges.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing
 here synchronises, with one exception: an ``edges`` rule with a trim or a loop crossfade changes what
 is delivered of each render, so ``deliver`` reads the spans the device found (8 int64 per render)
 before it sizes the later passes.  That is the chain's one host wait; fades alone wait for nothing.
@@ -11,7 +11,10 @@ A new export rule is a field of ``Delivery`` (after the last one, so the positio
 its row in ``RULES``, its lines in ``check`` and its step in ``deliver``; a pass that runs at the
 renders' rates is a closure handed to ``per_rate``.  The twelve dataclass fields and their order
 are pinned by the earlier rules' tests, so ``filter``, the rule after ``edges``, is a keyword of
-``Delivery`` and no dataclass field: ``Delivery(filter=f)``, seen by ``==`` and ``repr``.
+``Delivery`` and no dataclass field: ``Delivery(filter=f)``, seen by ``==`` and ``repr``; so is
+``stereo``, the rule between them in the chain.  From the stereo step on a render has one channel or
+two: ``deliver`` carries that count through every later pass, each of which takes it as a keyword
+that defaults to 2.
 """
 from __future__ import annotations
 
@@ -23,12 +26,13 @@ import numpy as np
 REPORT_DTYPE = np.dtype([(k, "<f8") for k in ("lufs", "lra", "lo", "hi", "max_momentary", "max_short", "peak",
                                               "true_peak", "dbtp")] + [("frames", "<i8"), ("rate", "<i8")])
 
-# The rules, each a field of Delivery (``filter``: its keyword): (the rule, the option that comes with it, why it works on one
+# The rules, each a field of Delivery (``filter``, ``stereo``: its keywords): (the rule, the option that comes with it, why it works on one
 # device only, whether results "stats" may ask for it).  ``dither``, ``dither_seed`` and ``shape`` are
 # options of ``bits`` that ask for nothing alone, so they have no row.
 RULES = (("sr", "peak", " (multi.py sizes its shared memory by out_n)", False), ("lufs", "ceiling", "", False),
          ("true_peak", None, "", False), ("bits", None, "", False), ("limiter", None, "", False),
-         ("report", None, "", False), ("edges", None, "", False), ("filter", None, "", False))
+         ("report", None, "", False), ("stereo", None, "", False), ("edges", None, "", False),
+         ("filter", None, "", False))
 
 
 @dataclass
@@ -51,7 +55,8 @@ class DeliveryFields:
         """Read the reports ``deliver`` left on the device into ``report``, in render order;
         the caller has waited for the renders' copy, so this waits for nothing new."""
         for pending in self._pending:
-            self.report.extend(pending.rows())
+            sink = getattr(pending, "sink", None)             # a stereo rule's meter rows go to its own list
+            (self.report if sink is None else sink).extend(pending.rows())
         self._pending.clear()
 
     def limiter_ms(self):
@@ -149,6 +154,21 @@ class DeliveryFields:
             except ValueError as e:
                 raise ValueError(f"{p}filter: {e}") from None
         self.one_device(p, n_devices, ("filter",))
+        if self.stereo is not None:
+            from .loudness import _check_rate
+            from .stereo import Stereo
+            if not isinstance(self.stereo, Stereo):
+                raise ValueError(f"{p}stereo must be None or a Stereo")
+            try:
+                self.stereo.check()
+            except ValueError as e:
+                raise ValueError(f"{p}stereo: {e}") from None
+            for rate in ([self.sr] if self.sr is not None else rates) if self.stereo.metering() else ():
+                try:
+                    _check_rate(rate)
+                except ValueError:
+                    raise ValueError(f"{p}stereo meters rates that are multiples of 10, at least 4000") from None
+        self.one_device(p, n_devices, ("stereo",))
         if results == "stats":
             for rule, _, _, with_stats in RULES:
                 if not with_stats and getattr(self, rule) is not None:
@@ -157,23 +177,30 @@ class DeliveryFields:
 
 class Delivery(DeliveryFields):
     """What a front end delivers: DeliveryFields' rules, given as they always were, and after them
-    ``filter``, a filter.Filter whose biquad cascade runs in front of the edges and the level rules.
-    It is given by keyword only and is not a dataclass field (``dataclasses.fields`` and
-    ``dataclasses.replace`` do not see it; ``==`` and ``repr`` do)."""
+    ``filter``, a filter.Filter whose biquad cascade runs in front of the edges and the level rules,
+    and ``stereo``, a stereo.Stereo whose meter, image matrix or mono fold runs between the filter and
+    the edges.  They are given by keyword only and are not dataclass fields (``dataclasses.fields``
+    and ``dataclasses.replace`` do not see them; ``==`` and ``repr`` do)."""
     filter = None
+    stereo = None
 
-    def __init__(self, *args, filter=None, **kw):
+    def __init__(self, *args, filter=None, stereo=None, **kw):
         super().__init__(*args, **kw)
         self.filter = filter
+        self.stereo = stereo
 
     def __eq__(self, other):
         same = DeliveryFields.__eq__(self, other)
-        return same if same is NotImplemented else same and self.filter == other.filter
+        return same if same is NotImplemented else same and self.filter == other.filter and self.stereo == other.stereo
 
     __hash__ = None
 
     def __repr__(self):
-        return DeliveryFields.__repr__(self)[:-1] + f", filter={self.filter!r})"
+        return DeliveryFields.__repr__(self)[:-1] + f", filter={self.filter!r}, stereo={self.stereo!r})"
+
+    def channels(self):
+        """The channels of what is delivered: 1 when the stereo rule folds to mono, else 2."""
+        return 1 if self.stereo is not None and self.stereo.channels == 1 else 2
 
 
 def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
@@ -181,7 +208,10 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     at frame offsets[i] with lens[i] frames at rates[i] Hz): resampled to ``delivery.sr``
     (``peaks``: resample_packed's), filtered by ``delivery.filter`` (filter_packed: in front of the edges, so
     that a trim sees the filtered signal and the fades still end at zero, and in front of the level rules, so
-    that loudness, true peak, limiter and report measure what is delivered), its ends shaped by ``delivery.edges`` (edges_packed; from there
+    that loudness, true peak, limiter and report measure what is delivered), metered, shaped or folded
+    to mono by ``delivery.stereo`` (stereo_packed: after the filter, because DC and rumble are correlation,
+    and in front of the edges and the level rules, because a fold changes the level they must see; from there
+    on a render has ``delivery.channels()`` channels, (frames, 1) when folded), its ends shaped by ``delivery.edges`` (edges_packed; from there
     on a render is the span that rule left of it), levelled at the rate delivered, metered as delivered when
     ``delivery.report`` is a list (report_packed; ``delivery.flush_report`` reads the rows once
     the caller has waited for its copy), quantised with the dither streams
@@ -196,14 +226,17 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
         rates = [int(d.sr)] * len(lens)
     if d.filter is not None:
         filter_packed(eng, out, offsets, lens, rates, d.filter)
+    ch = 2
+    if d.stereo is not None:
+        out, offsets, ch = stereo_packed(eng, out, offsets, lens, rates, d.stereo, pending=d._pending)
     if d.edges is not None:
-        offsets, lens, _ = edges_packed(eng, out, offsets, lens, rates, d.edges)
-    _level(eng, out, offsets, lens, rates, d.lufs, d.ceiling, d.true_peak, d.limiter_ms())
+        offsets, lens, _ = edges_packed(eng, out, offsets, lens, rates, d.edges, channels=ch)
+    _level(eng, out, offsets, lens, rates, d.lufs, d.ceiling, d.true_peak, d.limiter_ms(), channels=ch)
     if d.report is not None:
-        d._pending.append(report_packed(eng, out, offsets, lens, rates))
+        d._pending.append(report_packed(eng, out, offsets, lens, rates, channels=ch))
     if d.bits is None:
         return out, offsets, lens, None
-    return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys, d.shape)
+    return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys, d.shape, channels=ch)
 
 
 def _extents(offsets, lens, rates):
@@ -274,8 +307,8 @@ def resample_packed(eng, out, offsets, lens, sr_in, out_sr, peaks=None):
     return y, y_off, y_lens
 
 
-def edges_packed(eng, y, offsets, lens, rates, edges):
-    """Shape the ends of renders lying in a device tensor ((frames, 2) float32, render i at frame
+def edges_packed(eng, y, offsets, lens, rates, edges, channels=2):
+    """Shape the ends of renders lying in a device tensor ((frames, ``channels``) float32, render i at frame
     offsets[i] with lens[i] frames at rates[i] Hz) where they lie: msg_edges per distinct rate
     (edges.py: the milliseconds of ``edges`` are frames at the render's rate).  Nothing is
     moved.  Returns (offsets, lens, rec): where each render's delivered span lies, and the
@@ -284,7 +317,7 @@ def edges_packed(eng, y, offsets, lens, rates, edges):
     extents come back as they were and nothing waits."""
     from .edges import records
     offsets, lens, rates = _extents(offsets, lens, rates)
-    rec = per_rate(eng, y, offsets, lens, rates, lambda off, cnt, rate: eng.edges(y, off, cnt, 2, rate, edges), 8,
+    rec = per_rate(eng, y, offsets, lens, rates, lambda off, cnt, rate: eng.edges(y, off, cnt, channels, rate, edges), 8,
                    eng.torch.int64)
     if not edges.moves_span() or not len(rates):
         return offsets, lens, rec
@@ -303,8 +336,44 @@ def filter_packed(eng, y, offsets, lens, rates, flt):
     per_rate(eng, y, offsets, lens, rates, run, ())
 
 
-def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None, true_peak=None):
-    """Bring renders lying in a device tensor ((frames, 2) float32, render i at frame
+class MeterRows:
+    """The device records of one stereo_packed call's meter, in render order, and the list they are
+    for; ``rows`` copies them to the host with the derived columns (it waits for them)."""
+
+    def __init__(self, rec, sink):
+        self.rec, self.sink = rec, sink
+
+    def rows(self):
+        from .stereo import records
+        return records(self.rec)
+
+
+def stereo_packed(eng, y, offsets, lens, rates, stereo, pending=None):
+    """Meter, shape or fold renders lying in a device tensor ((frames, 2) float32, render i at frame
+    offsets[i] with lens[i] frames at rates[i] Hz) with ``stereo``, a stereo.Stereo.  It meters first,
+    msg_stereo_meter per distinct rate (the blocks are 400 ms at the render's rate), when
+    ``stereo.meter`` is a list or ``stereo.invert == "auto"``; then one msg_stereo call applies the
+    image to every render, the polarity of each taken from its record on the device.  Returns
+    (buffer, offsets, channels): y shaped in place with the offsets as they were and 2, or a new
+    (frames, 1) tensor with the folded renders back to back, their offsets and 1.  The meter's rows:
+    with ``pending`` (a list, ``Delivery._pending``) a MeterRows is left there and nothing waits;
+    without it they are read into ``stereo.meter`` here, the one host wait."""
+    offsets, lens, rates = _extents(offsets, lens, rates)
+    rec = None
+    if stereo.metering():
+        rec = per_rate(eng, y, offsets, lens, rates, lambda off, cnt, rate: eng.stereo_meter(y, off, cnt, rate), 8)
+        if stereo.meter is not None:
+            rows = MeterRows(rec, stereo.meter)
+            if pending is None:
+                stereo.meter.extend(rows.rows())
+            else:
+                pending.append(rows)
+    out, out_off = eng.stereo(y, offsets, lens, stereo, rec=rec if stereo.invert == "auto" else None)
+    return out, out_off, stereo.channels
+
+
+def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None, true_peak=None, channels=2):
+    """Bring renders lying in a device tensor ((frames, ``channels``) float32, render i at frame
     offsets[i] with lens[i] frames at rates[i] Hz) to ``target_lufs`` where they lie:
     msg_loudness then msg_loudness_gain per distinct rate, the gain formed on the
     device from each render's record (no host synchronise).  ``ceiling``: a linear
@@ -313,12 +382,12 @@ def loudness_packed(eng, y, offsets, lens, rates, target_lufs, ceiling=None, tru
     measured too and msg_truepeak_gain forms the one gain from both records.  Scales y
     in place and returns the device records in render order (engine.Engine.loudness)."""
     def level(off, cnt, rate):
-        r = eng.loudness(y, off, cnt, 2, rate)
+        r = eng.loudness(y, off, cnt, channels, rate)
         if true_peak is None:
-            eng.loudness_gain(y, off, cnt, 2, r, float(target_lufs), ceiling)
+            eng.loudness_gain(y, off, cnt, channels, r, float(target_lufs), ceiling)
         else:
-            t = eng.true_peak(y, off, cnt, 2, rate)
-            eng.true_peak_gain(y, off, cnt, 2, t, r, float(target_lufs), _dbtp(true_peak), ceiling)
+            t = eng.true_peak(y, off, cnt, channels, rate)
+            eng.true_peak_gain(y, off, cnt, channels, t, r, float(target_lufs), _dbtp(true_peak), ceiling)
         return r
     return per_rate(eng, y, offsets, lens, rates, level, 5)
 
@@ -331,20 +400,20 @@ def _dbtp(true_peak):
     return 10.0 ** (v / 20.0)
 
 
-def truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling=None):
+def truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling=None, channels=2):
     """Hold renders lying in a device tensor (as loudness_packed) under ``true_peak`` dBTP
     where they lie, with no loudness target: msg_truepeak then msg_truepeak_gain per
     distinct rate, the gain (1 where the ceiling does not bind) formed on the device.
     ``ceiling``: a linear sample peak as well (None: no limit).  Scales y in place and
     returns the device records in render order (engine.Engine.true_peak)."""
     def level(off, cnt, rate):
-        t = eng.true_peak(y, off, cnt, 2, rate)
-        eng.true_peak_gain(y, off, cnt, 2, t, None, None, _dbtp(true_peak), ceiling)
+        t = eng.true_peak(y, off, cnt, channels, rate)
+        eng.true_peak_gain(y, off, cnt, channels, t, None, None, _dbtp(true_peak), ceiling)
         return t
     return per_rate(eng, y, offsets, lens, rates, level, 5)
 
 
-def limiter_packed(eng, y, offsets, lens, rates, true_peak, lookahead_ms, lufs=None, ceiling=None):
+def limiter_packed(eng, y, offsets, lens, rates, true_peak, lookahead_ms, lufs=None, ceiling=None, channels=2):
     """Hold renders lying in a device tensor (as loudness_packed) under ``true_peak`` dBTP with
     the look-ahead limiter instead of one static gain, per distinct rate: levelled to
     ``lufs`` first when given (msg_loudness, msg_loudness_gain with no ceiling), then
@@ -358,23 +427,23 @@ def limiter_packed(eng, y, offsets, lens, rates, true_peak, lookahead_ms, lufs=N
 
     def level(off, cnt, rate):
         if lufs is not None:
-            r = eng.loudness(y, off, cnt, 2, rate)
-            eng.loudness_gain(y, off, cnt, 2, r, float(lufs), None)
-        t = eng.true_peak(y, off, cnt, 2, rate)
-        lim = eng.limit(y, off, cnt, 2, rate, c, lookahead_frames(rate, lookahead_ms), tp_rec=t)
-        t2 = eng.true_peak(y, off, cnt, 2, rate)
-        eng.true_peak_gain(y, off, cnt, 2, t2, None, None, c, ceiling)
+            r = eng.loudness(y, off, cnt, channels, rate)
+            eng.loudness_gain(y, off, cnt, channels, r, float(lufs), None)
+        t = eng.true_peak(y, off, cnt, channels, rate)
+        lim = eng.limit(y, off, cnt, channels, rate, c, lookahead_frames(rate, lookahead_ms), tp_rec=t)
+        t2 = eng.true_peak(y, off, cnt, channels, rate)
+        eng.true_peak_gain(y, off, cnt, channels, t2, None, None, c, ceiling)
         return lim
     return per_rate(eng, y, offsets, lens, rates, level, 4)
 
 
-def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak, limiter_ms=None):
+def _level(eng, y, offsets, lens, rates, lufs, ceiling, true_peak, limiter_ms=None, channels=2):
     if limiter_ms is not None:
-        limiter_packed(eng, y, offsets, lens, rates, true_peak, limiter_ms, lufs, ceiling)
+        limiter_packed(eng, y, offsets, lens, rates, true_peak, limiter_ms, lufs, ceiling, channels)
     elif lufs is not None:
-        loudness_packed(eng, y, offsets, lens, rates, lufs, ceiling, true_peak)
+        loudness_packed(eng, y, offsets, lens, rates, lufs, ceiling, true_peak, channels)
     elif true_peak is not None:
-        truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling)
+        truepeak_packed(eng, y, offsets, lens, rates, true_peak, ceiling, channels)
 
 
 class Report:
@@ -402,13 +471,13 @@ class Report:
         return out
 
 
-def report_packed(eng, y, offsets, lens, rates):
+def report_packed(eng, y, offsets, lens, rates, channels=2):
     """The delivery meters of renders lying in a device tensor (as loudness_packed), as they are
     delivered: per distinct rate one msg_loudness_range call (integrated loudness, loudness
     range, maximum momentary and short-term loudness) and msg_truepeak (sample peak, true
     peak, dBTP).  Changes no sample; returns a Report, no host synchronise."""
     def meter(off, cnt, rate):
-        return eng.loudness_range(y, off, cnt, 2, rate) + (eng.true_peak(y, off, cnt, 2, rate),)
+        return eng.loudness_range(y, off, cnt, channels, rate) + (eng.true_peak(y, off, cnt, channels, rate),)
     return Report(*per_rate(eng, y, offsets, lens, rates, meter, (5, 12, 5)), lens, rates)
 
 
@@ -422,7 +491,7 @@ def write_report_csv(path, names, rows):
             w.writerow([name] + [repr(row[k].item()) for k in REPORT_DTYPE.names])
 
 
-def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=None, shape=None):
+def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=None, shape=None, channels=2):
     """Renders lying in a device tensor (as loudness_packed) as ``bits``-bit PCM, quantised
     and packed on the device after every level rule (msg_quantize, pcm.py): render i
     takes its dither from the stream (seed, keys[i]); ``shape``: noise-shaped dither
@@ -430,12 +499,12 @@ def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=Non
     each render's byte offset and length in it, and the device records (no host synchronise)."""
     offsets = np.asarray(offsets, dtype=np.int64)
     lens = np.asarray(lens, dtype=np.int64)
-    out, byte_off, rec = eng.quantize(y, offsets, lens, 2, bits, dither, seed, keys, shape=shape)
-    return out, byte_off, lens * (2 * (int(bits) // 8)), rec
+    out, byte_off, rec = eng.quantize(y, offsets, lens, channels, bits, dither, seed, keys, shape=shape)
+    return out, byte_off, lens * (int(channels) * (int(bits) // 8)), rec
 
 
-def unpack_all(host, byte_off, nbytes, bits):
-    """The integer arrays (frames, 2) of quantize_packed's bytes once they are on the host."""
+def unpack_all(host, byte_off, nbytes, bits, channels=2):
+    """The integer arrays (frames, ``channels``) of quantize_packed's bytes once they are on the host."""
     from .pcm import unpack
-    frame = 2 * (int(bits) // 8)
-    return [unpack(host[int(o):int(o) + int(b)], bits, (int(b) // frame, 2)) for o, b in zip(byte_off, nbytes)]
+    frame = int(channels) * (int(bits) // 8)
+    return [unpack(host[int(o):int(o) + int(b)], bits, (int(b) // frame, int(channels))) for o, b in zip(byte_off, nbytes)]

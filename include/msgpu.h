@@ -558,6 +558,43 @@ int msg_filter(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offs
  * frames of `channels` interleaved words); needs no device. */
 int msg_filter_host(float* x, int32_t channels, int64_t n, const msg_filter_opts* opts);
 
+/* The stereo image of signals lying in HBM (csrc/image.h holds the definition, DESIGN.md 4k the
+ * kernels).  The meter: over the interleaved L/R float32 frames of a signal, in float64 (the
+ * products are exact), sll = sum L^2, srr = sum R^2, slr = sum L R; corr = slr / sqrt(sll srr),
+ * 0 when either sum is 0.  Blocks are msg_loudness's (hop = sr / 10, block j = frames
+ * [j hop, j hop + 4 hop), complete blocks only); a block is kept when its SLL > 0, SRR > 0 and
+ * SLL + SRR > 8 hop 1e-7 (a mean square per channel above -70 dBFS); corr_min is the smallest
+ * correlation of a kept block and corr_min_block its index, the lowest on a tie; with no kept
+ * block corr_min = corr and corr_min_block = -1.  Counts and the index are float64 too: the record
+ * is eight float64 and has no msg_sizeof entry.  The sums
+ * fold in one fixed order with no atomics (tiles that never straddle a hop, hops in order, a
+ * block ((h0 + h1) + h2) + h3): a record is the same bits from run to run, alone or in any
+ * batch, and differs from msg_stereo_meter_host, the sequential loop, by float64 roundings. */
+typedef struct msg_stereo_rec {
+    double sll, srr, slr, corr, corr_min, corr_min_block, blocks_kept, blocks;
+} msg_stereo_rec;
+/* Signals as for msg_loudness; channels must be 2 and sr a multiple of 10, at least 4000
+ * (MSG_E_VALUE).  One read of the samples; enqueued on stream with no host synchronise; one call
+ * in flight per context. */
+int msg_stereo_meter(msg_ctx* ctx, const float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                     int32_t n_signals, int32_t sr, msg_stereo_rec* rec_dev, void* stream);
+int msg_stereo_meter_host(const float* x, int32_t channels, int64_t n, int32_t sr, msg_stereo_rec* rec);
+/* One float32 2 x 2 matrix (m00 m01 m10 m11) over every frame of every signal, in place:
+ *   L' = fma(m00, L, round32(m01 R)),  R' = fma(m10, L, round32(m11 R)),
+ * or, fold not null, one row (f0 f1) into a mono buffer, y = fma(f0, L, round32(f1 R)) at
+ * y_dev + out_offsets[i], the input unchanged and matrix not read.  Host and device give the
+ * same bits.  rec_dev: null, or the signals' msg_stereo_meter records: a signal with corr < 0
+ * has m01, m11 and f1 negated on the device, its right channel inverted first.  The identity
+ * with no fold and no records launches nothing.  channels must be 2, the matrix finite, and no
+ * output may overlap an input or another signal (MSG_E_VALUE). */
+int msg_stereo(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+               int32_t n_signals, const float* matrix, const float* fold, float* y_dev, const int64_t* out_offsets,
+               const msg_stereo_rec* rec_dev, void* stream);
+/* The same over one signal in host memory (x: n stereo frames; y: n floats when fold is given);
+ * rec: null or one record; needs no device. */
+int msg_stereo_host(float* x, int32_t channels, int64_t n, const float* matrix, const float* fold, float* y,
+                    const msg_stereo_rec* rec);
+
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
 int msg_rng_raw(uint64_t seed, uint64_t* out, int64_t n);
