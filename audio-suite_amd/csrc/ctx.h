@@ -394,6 +394,12 @@ struct msg_ctx {
     // msg_stereo_meter / msg_stereo: signal extents + tile bases (+ the fold's output offsets), per-tile sums
     DevBuf<int64_t> img_meta;
     DevBuf<double> img_part;
+    // msg_dynamics: signal extents + tile bases; per tile the two summaries and the two carries; per
+    // tile the non-finite flag; per signal the state; with a hold, per tile the demands of the
+    // hold_frames before it
+    DevBuf<int64_t> dyn_meta, dyn_carry, dyn_halo;
+    DevBuf<uint32_t> dyn_flag;
+    DevBuf<int32_t> dyn_state;
 
     // What must come first and in this order; the members' destructors follow.
     ~msg_ctx() {

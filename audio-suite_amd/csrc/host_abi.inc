@@ -3,12 +3,13 @@
 // the host references of the render digest (digest.h), of the loudness and true-peak
 // measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantisers (pcm.h, pcm_shape.h) and of the look-ahead
 // limiter (limit.h), of the edges pass (edges.h), of the delivery filter (filter.h) and of the stereo
-// meter and image (image.h).  Included
+// meter and image (image.h), and of the compressor (dynamics.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
 // named above (DigestPart / dg_host, LoudRec / ld_host, LRangeRec / lr_host, TruePeakRec / tp_host, PcmRec / pcm_host,
-// LimitRec / lim_host, EdgesRec / edg_host, FilterOpts / fl_host, ImageRec / img_meter_host / img_host).
+// LimitRec / lim_host, EdgesRec / edg_host, FilterOpts / fl_host, ImageRec / img_meter_host / img_host,
+// DynRec / dyn_host).
 
 int64_t msg_sizeof(int32_t which) {
     switch (which) {
@@ -324,6 +325,53 @@ int msg_stereo_host(float* x, int32_t channels, int64_t n, const float* matrix, 
     const bool flip = rec && rec->corr < 0.0;
     if (!fold && !flip && img_identity(matrix)) return MSG_OK;     // the identity touches nothing
     img_host(x, n, matrix, fold, y, flip);
+    return MSG_OK;
+}
+
+// The value checks msg_dynamics and msg_dynamics_host share, and the kernels' parameters
+static int dyn_values(msg_ctx* ctx, const msg_dynamics_opts* opts, DynPar* par) {
+    static_assert(sizeof(DynOpts) == sizeof(msg_dynamics_opts), "DynOpts is msg_dynamics_opts");
+    static_assert(sizeof(DynRec) == sizeof(msg_dynamics_rec), "DynRec is msg_dynamics_rec");
+    DynOpts o;
+    std::memcpy(&o, opts, sizeof(o));
+    if (const char* why = dyn_refused(o)) return fail(ctx, MSG_E_VALUE, why);
+    if (o.hold_frames > DYN_HOLD_MAX) return fail(ctx, MSG_E_UNSUPPORTED, "hold beyond 4096 frames");
+    *par = dyn_par(o);
+    return MSG_OK;
+}
+
+// The compressor over one signal in host memory, in place: the definition of dynamics.h as one
+// sequential loop (dyn_host), the device's samples and record to the bit
+int msg_dynamics_host(float* x, int32_t channels, int64_t n, const msg_dynamics_opts* opts, msg_dynamics_rec* rec) {
+    if (!rec || !opts || n < 0 || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    DynPar par;
+    if (const int rc = dyn_values(nullptr, opts, &par)) return rc;
+    DynRec r;
+    dyn_host(x, channels, n, par, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The same, and the envelope E per frame into env (n words).  For the tests; not part of the ABI.
+int msg_debug_dynamics_env(float* x, int32_t channels, int64_t n, const msg_dynamics_opts* opts, msg_dynamics_rec* rec,
+                           int64_t* env) {
+    if (!rec || !opts || n < 0 || (n > 0 && (!x || !env))) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    DynPar par;
+    if (const int rc = dyn_values(nullptr, opts, &par)) return rc;
+    DynRec r;
+    dyn_host(x, channels, n, par, &r, env);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+// dyn_log2 over n positive floats and dyn_exp2 over n doubles.  For the tests; not part of the ABI.
+int msg_debug_dyn_log2(const float* p, double* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) out[i] = dyn_log2(p[i]);
+    return MSG_OK;
+}
+int msg_debug_dyn_exp2(const double* x, double* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) out[i] = dyn_exp2(x[i]);
     return MSG_OK;
 }
 

@@ -260,3 +260,14 @@ hipError_t launch_image_meter(int n_sig, unsigned tiles, hipStream_t s, const fl
 // records, whose corr < 0 inverts the right channel of that signal first
 hipError_t launch_image_apply(int n_sig, unsigned tiles, hipStream_t s, float* x, const int64_t* meta, const float* m,
                               const float* fold, float* y, const void* rec);
+
+// compressor (kernels_dynamics.h): the first sweep over tiles of DYN_TILE frames writes every tile's
+// two summaries and its non-finite flag, the scan turns them into the carries that enter every tile,
+// folds the flags into state and initialises rec (msg_dynamics_rec records), the second sweep
+// compresses in place and folds the records.  meta: offsets, frames, n_sig + 1 first tiles
+// (dyn_tiles); carry: 4 words per tile; flag: one word per tile; state: one word per signal; halo:
+// with a hold, hold_frames words per tile (the demands before the tile, saved by the first sweep), else null
+struct DynPar;
+void dynamics_init_attrs();
+hipError_t launch_dynamics(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
+                           const DynPar& par, int64_t* carry, uint32_t* flag, int32_t* state, void* rec, int64_t* halo);

@@ -42,6 +42,7 @@
 #include "edges.h"
 #include "filter.h"
 #include "image.h"
+#include "dynamics.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"
@@ -469,6 +470,7 @@ msg_ctx* msg_create(int device_ordinal) {
     stereo_odd_init_attrs();
     fir64_init_attrs();
     limit_init_attrs();
+    dynamics_init_attrs();
     return ctx.release();
 }
 

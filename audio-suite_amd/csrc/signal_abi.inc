@@ -1,7 +1,7 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
 // msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_quantize_shaped, msg_limit,
-// msg_edges, msg_filter, msg_stereo_meter, msg_stereo.
+// msg_edges, msg_filter, msg_stereo_meter, msg_stereo, msg_dynamics.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -490,5 +490,31 @@ int msg_stereo(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offs
     if (c.tiles == 0 || (!fold && !rec_dev && img_identity(matrix))) return MSG_OK;   // the identity launches nothing
     if (const int rc = c.open(ctx->img_meta)) return rc;
     HIPCHK(ctx, launch_image_apply(n_signals, (unsigned)c.tiles, c.s, x_dev, ctx->img_meta.p, matrix, fold, y_dev, rec_dev));
+    return c.finish();
+}
+
+int msg_dynamics(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n, int32_t n_signals,
+                 const msg_dynamics_opts* opts, msg_dynamics_rec* rec_dev, void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && opts && rec_dev, n_signals, channels)) return rc;
+    DynPar par;
+    if (const int rc = dyn_values(ctx, opts, &par)) return rc;
+    if (const int rc = sig_aligned(ctx, channels, x_dev)) return rc;
+    if (n_signals == 0) return MSG_OK;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, dyn_tiles, "signal", "dynamics")) return rc;
+    if (c.tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    // the pass writes where it reads: two signals sharing a frame would compress each other's output
+    SigRanges ranges;
+    for (int i = 0; i < n_signals; ++i)
+        if (n[i] > 0) ranges.emplace_back(offsets[i], offsets[i] + n[i]);
+    if (const int rc = sig_disjoint(ctx, ranges, "signal")) return rc;
+    if (const int rc = c.open(ctx->dyn_meta)) return rc;
+    HIPCHK(ctx, ctx->dyn_carry.ensure(c.parts() * 4));
+    HIPCHK(ctx, ctx->dyn_flag.ensure(c.parts()));
+    HIPCHK(ctx, ctx->dyn_state.ensure((size_t)n_signals));
+    if (par.hold > 0) HIPCHK(ctx, ctx->dyn_halo.ensure(c.parts() * (size_t)par.hold));
+    // the scan runs without a tile too: it initialises the records
+    HIPCHK(ctx, launch_dynamics(n_signals, channels, (unsigned)c.tiles, c.s, x_dev, ctx->dyn_meta.p, par, ctx->dyn_carry.p,
+                                ctx->dyn_flag.p, ctx->dyn_state.p, rec_dev, par.hold > 0 ? ctx->dyn_halo.p : nullptr));
     return c.finish();
 }

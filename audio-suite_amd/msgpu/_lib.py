@@ -129,6 +129,16 @@ class MsgStereoRec(C.Structure):
                                           "blocks")]
 
 
+class MsgDynamicsOpts(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("threshold_db", "ratio", "knee_db", "makeup_db")] + \
+               [("attack_step", C.c_int64), ("release_step", C.c_int64), ("hold_frames", C.c_int32), ("flags", C.c_int32)]
+
+
+class MsgDynamicsRec(C.Structure):
+    _fields_ = [("max_e", C.c_int64), ("sum_e16", C.c_int64), ("reduced_frames", C.c_int64), ("state", C.c_int32),
+                ("hold_frames", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -208,6 +218,9 @@ _PROTOS = {
     "msg_stereo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "msg_stereo_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "msg_dynamics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                               C.POINTER(MsgDynamicsOpts), C.c_void_p, C.c_void_p]),
+    "msg_dynamics_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(MsgDynamicsOpts), C.c_void_p]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),

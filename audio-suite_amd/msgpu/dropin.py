@@ -95,7 +95,8 @@ def _out_peaks(params_list, out_peak):
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
                  out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
-                 out_limiter=None, out_report=None, out_shape=None, out_stereo=None, out_filter=None, out_edges=None):
+                 out_limiter=None, out_report=None, out_shape=None, out_dynamics=None, out_stereo=None, out_filter=None,
+                 out_edges=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -131,10 +132,14 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     one row per render, read with the report's rows), a width, balance, swap or polarity matrix over
     every frame (``invert="auto"`` repairs the renders whose correlation is negative, on the device),
     and ``channels=1``, the fold to mono in HBM, after which every later rule, the report and the
-    quantiser work on the mono render and the arrays and tensors are (n, 1)."""
+    quantiser work on the mono render and the arrays and tensors are (n, 1).  ``out_dynamics``: a
+    dynamics.Dynamics (export.dynamics_packed), after the stereo rule and before the edges and the level
+    rules: every render compressed in HBM (threshold, ratio, soft knee, linear-in-dB attack, hold and
+    release, makeup), so a report after it shows the loudness range come down."""
     delivery = Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak,
                         bits=out_bits, dither=out_dither, dither_seed=out_dither_seed, limiter=out_limiter,
-                        report=out_report, shape=out_shape, edges=out_edges, filter=out_filter, stereo=out_stereo)
+                        report=out_report, shape=out_shape, edges=out_edges, filter=out_filter, stereo=out_stereo,
+                        dynamics=out_dynamics)
     params_list = list(params_list)
     delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)

@@ -431,6 +431,20 @@ class Engine:
                           stream=stream)
         return out, out_off
 
+    def dynamics(self, x, offsets, lens, channels, sr, dyn, stream=None):
+        """msg_dynamics: the compressor of a dynamics.Dynamics (milliseconds taken at ``sr`` Hz) over
+        signals lying in a device float32 tensor (as Engine.true_peak), in place.  Returns the device
+        records, an int64 tensor (signals, 4) whose rows are msg_dynamics_rec (dynamics.records reads
+        them on the host); enqueued on ``stream``, no host synchronise."""
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        opts = dyn.opts(sr)
+        rec = self.torch.empty((int(off.size), 4), dtype=self.torch.int64, device=x.device)
+        if not off.size:                      # no signal: no record to point at
+            return rec
+        self._signal_call(L.lib().msg_dynamics, x, channels, off, cnt, C.byref(opts), C.c_void_p(rec.data_ptr()),
+                          stream=stream)
+        return rec
+
     def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None,
                  shape=None):
         """msg_quantize of signals lying in a device float32 tensor (as Engine.true_peak):

@@ -20,6 +20,7 @@
  *   msg_quantize     16/24-bit PCM with TPDF dither, packed in HBM  (sf.write's subtype, MS:1589)
  *   msg_quantize_shaped  the same with noise-shaped dither (error feedback)  (no counterpart)
  *   msg_limit        look-ahead true-peak limiter in HBM            (no counterpart)
+ *   msg_dynamics     compressor in HBM, an exact integer envelope   (no counterpart)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
 #ifndef MSGPU_H
@@ -594,6 +595,49 @@ int msg_stereo(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offs
  * rec: null or one record; needs no device. */
 int msg_stereo_host(float* x, int32_t channels, int64_t n, const float* matrix, const float* fold, float* y,
                     const msg_stereo_rec* rec);
+
+/* A compressor over signals lying in HBM, in place (csrc/dynamics.h holds the definition,
+ * DESIGN.md 4l the kernels).  The channels are linked: p = max over the channels of |x| per
+ * frame.  Every envelope value is an int64 in [0, 2^40] in units of 2^-32 dB.  The demand d is 0
+ * for p <= p0, the float32 at or just under the level of threshold_db - knee_db / 2, and otherwise
+ * the soft-knee curve (Giannoulis, Massberg and Reiss 2012) of over = 20 log10 p - threshold_db
+ * with slope 1 - 1 / ratio, in float64 by the library's own log2, rounded to the nearest unit.
+ * dh is the maximum of d over the last hold_frames + 1 frames.  The ballistics are straight lines
+ * in dB: the release F[f] = max(F[f - 1] - release_step, dh[f]) runs forward from 0, the attack
+ * B[f] = max(B[f + 1] - attack_step, d[f]) backward from 0 (the pass is offline: the gain has
+ * fully arrived at a peak), and E = max(F, B) >= d.  The gain is
+ * (float) 2^((makeup_db - E 2^-32) log2(10) / 20) by the library's own exp2, the float64 rounded
+ * once, and y = x g in float32; a frame whose gain is 1 keeps its bits.  Integer max and + are
+ * associative and exact, so the device's tiled scans and msg_dynamics_host's sequential loop
+ * agree to the bit, samples and records, alone or in any batch.  A signal with a NaN or an
+ * infinity anywhere is left as it was, state 2.
+ *   max_e, sum_e16     the largest E, and the sum over frames of E >> 16
+ *   reduced_frames     frames with E > 0
+ *   state              0 untouched, 1 compressed (or given a makeup gain), 2 non-finite
+ * A step is round(10 2^32 / frames), frames what the gain takes to move 10 dB; 2^40 is instant.
+ * Neither struct has a msg_sizeof entry. */
+typedef struct msg_dynamics_opts {
+    double threshold_db;       /* -150 .. 24 */
+    double ratio;              /* >= 1, +inf: a limiter's slope */
+    double knee_db;            /* 0 .. 48 */
+    double makeup_db;          /* -48 .. 48 */
+    int64_t attack_step, release_step;   /* 1 .. 2^40 units per frame */
+    int32_t hold_frames;       /* 0 .. 4096 */
+    int32_t flags;             /* 0 */
+} msg_dynamics_opts;
+typedef struct msg_dynamics_rec {
+    int64_t max_e, sum_e16, reduced_frames;
+    int32_t state, hold_frames;
+} msg_dynamics_rec;
+/* Signals as for msg_edges, which must not overlap.  A value of opts out of range: MSG_E_VALUE;
+ * hold_frames above 4096: MSG_E_UNSUPPORTED.  rec_dev: n_signals device records.  Two sweeps over
+ * the samples and a scan over tiles between them enqueue back to back on stream with no host
+ * synchronise; one call in flight per context. */
+int msg_dynamics(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                 int32_t n_signals, const msg_dynamics_opts* opts, msg_dynamics_rec* rec_dev, void* stream);
+/* The same definition as one sequential loop over one signal in host memory, in place (x: n
+ * frames of `channels` interleaved words); needs no device. */
+int msg_dynamics_host(float* x, int32_t channels, int64_t n, const msg_dynamics_opts* opts, msg_dynamics_rec* rec);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
