@@ -400,6 +400,12 @@ struct msg_ctx {
     DevBuf<int64_t> dyn_meta, dyn_carry, dyn_halo;
     DevBuf<uint32_t> dyn_flag;
     DevBuf<int32_t> dyn_state;
+    // msg_gate_apply: signal extents + tile bases; per tile the two summaries and the two carries; per
+    // tile its transfer (3 words) and the age that enters it; per tile the non-finite flag; per signal
+    // the state
+    DevBuf<int64_t> gate_meta, gate_carry, gate_trans;
+    DevBuf<uint32_t> gate_flag;
+    DevBuf<int32_t> gate_state;
 
     // What must come first and in this order; the members' destructors follow.
     ~msg_ctx() {

@@ -3,13 +3,13 @@
 // the host references of the render digest (digest.h), of the loudness and true-peak
 // measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantisers (pcm.h, pcm_shape.h) and of the look-ahead
 // limiter (limit.h), of the edges pass (edges.h), of the delivery filter (filter.h) and of the stereo
-// meter and image (image.h), and of the compressor (dynamics.h).  Included
+// meter and image (image.h), of the compressor (dynamics.h) and of the gate (gate.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
 // named above (DigestPart / dg_host, LoudRec / ld_host, LRangeRec / lr_host, TruePeakRec / tp_host, PcmRec / pcm_host,
 // LimitRec / lim_host, EdgesRec / edg_host, FilterOpts / fl_host, ImageRec / img_meter_host / img_host,
-// DynRec / dyn_host).
+// DynRec / dyn_host, GateRec / gate_host).
 
 int64_t msg_sizeof(int32_t which) {
     switch (which) {
@@ -372,6 +372,44 @@ int msg_debug_dyn_log2(const float* p, double* out, int64_t n) {
 }
 int msg_debug_dyn_exp2(const double* x, double* out, int64_t n) {
     for (int64_t i = 0; i < n; ++i) out[i] = dyn_exp2(x[i]);
+    return MSG_OK;
+}
+
+// The value checks msg_gate_apply and msg_gate_host share, and the kernels' parameters
+static int gate_values(msg_ctx* ctx, const msg_gate_opts* opts, GatePar* par) {
+    static_assert(sizeof(GateOpts) == sizeof(msg_gate_opts), "GateOpts is msg_gate_opts");
+    static_assert(sizeof(GateRec) == sizeof(msg_gate_rec), "GateRec is msg_gate_rec");
+    GateOpts o;
+    std::memcpy(&o, opts, sizeof(o));
+    if (const char* why = gate_refused(o)) return fail(ctx, MSG_E_VALUE, why);
+    *par = gate_par(o);
+    return MSG_OK;
+}
+
+// The gate over one signal in host memory, in place: the definition of gate.h as one sequential
+// loop (gate_host), the device's samples and record to the bit
+int msg_gate_host(float* x, int32_t channels, int64_t n, const msg_gate_opts* opts, msg_gate_rec* rec) {
+    if (!rec || !opts || n < 0 || (n > 0 && !x)) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    GatePar par;
+    if (const int rc = gate_values(nullptr, opts, &par)) return rc;
+    GateRec r;
+    gate_host(x, channels, n, par, &r);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The same, the envelope E per frame into env (n words) and the held state sh into held (n bytes).
+// For the tests; not part of the ABI.
+int msg_debug_gate_env(float* x, int32_t channels, int64_t n, const msg_gate_opts* opts, msg_gate_rec* rec, int64_t* env,
+                       uint8_t* held) {
+    if (!rec || !opts || n < 0 || (n > 0 && (!x || !env || !held))) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (channels != 1 && channels != 2) return fail(nullptr, MSG_E_VALUE, "channels must be 1 or 2");
+    GatePar par;
+    if (const int rc = gate_values(nullptr, opts, &par)) return rc;
+    GateRec r;
+    gate_host(x, channels, n, par, &r, env, held);
+    std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }
 

@@ -6,7 +6,7 @@
 // msg_truepeak_host), of the PCM quantiser (pcm.h, msg_quantize_host) and of the
 // look-ahead limiter (limit.h, msg_limit_host), of the edges pass (edges.h, msg_edges_host) and of the
 // stereo meter and image (image.h, msg_stereo_meter_host, msg_stereo_host) and of the compressor
-// (dynamics.h, msg_dynamics_host),
+// (dynamics.h, msg_dynamics_host) and of the gate (gate.h, msg_gate_host),
 // compiled by g++ with -fsanitize=address,undefined into
 // msgpu/libmsgpu_hostsan.so.  The device entry points are stubs that fail with
 // MSG_E_DEVICE, so the ctypes binding (_lib.py) loads this library unchanged
@@ -34,6 +34,7 @@
 #include "filter.h"
 #include "image.h"
 #include "dynamics.h"
+#include "gate.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -131,6 +132,10 @@ int msg_stereo(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_
 }
 int msg_dynamics(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, const msg_dynamics_opts*,
                  msg_dynamics_rec*, void*) {
+    return no_device();
+}
+int msg_gate_apply(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, const msg_gate_opts*, msg_gate_rec*,
+                   void*) {
     return no_device();
 }
 #include "host_abi.inc"

@@ -271,3 +271,13 @@ struct DynPar;
 void dynamics_init_attrs();
 hipError_t launch_dynamics(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
                            const DynPar& par, int64_t* carry, uint32_t* flag, int32_t* state, void* rec, int64_t* halo);
+
+// gate (kernels_gate.h): with hysteresis or a hold a read-only state sweep writes every tile's
+// transfer and a scan turns them into the age that enters every tile; then, as the compressor, the
+// first sweep writes every tile's two summaries and its non-finite flag, the scan turns them into
+// the carries, folds the flags into state and initialises rec (msg_gate_rec records), the second
+// sweep gates in place and folds the records.  meta: offsets, frames, n_sig + 1 first tiles
+// (dyn_tiles); carry, trans: 4 words per tile each; flag: one word per tile; state: one word per signal
+struct GatePar;
+hipError_t launch_gate(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
+                       const GatePar& par, int64_t* carry, int64_t* trans, uint32_t* flag, int32_t* state, void* rec);

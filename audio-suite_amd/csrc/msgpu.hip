@@ -43,6 +43,7 @@
 #include "filter.h"
 #include "image.h"
 #include "dynamics.h"
+#include "gate.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"

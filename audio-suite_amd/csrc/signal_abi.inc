@@ -1,7 +1,7 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
 // msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_quantize_shaped, msg_limit,
-// msg_edges, msg_filter, msg_stereo_meter, msg_stereo, msg_dynamics.
+// msg_edges, msg_filter, msg_stereo_meter, msg_stereo, msg_dynamics, msg_gate_apply.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -516,5 +516,31 @@ int msg_dynamics(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* of
     // the scan runs without a tile too: it initialises the records
     HIPCHK(ctx, launch_dynamics(n_signals, channels, (unsigned)c.tiles, c.s, x_dev, ctx->dyn_meta.p, par, ctx->dyn_carry.p,
                                 ctx->dyn_flag.p, ctx->dyn_state.p, rec_dev, par.hold > 0 ? ctx->dyn_halo.p : nullptr));
+    return c.finish();
+}
+
+int msg_gate_apply(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n, int32_t n_signals,
+                   const msg_gate_opts* opts, msg_gate_rec* rec_dev, void* stream) {
+    if (const int rc = sig_args(ctx, offsets && n && opts && rec_dev, n_signals, channels)) return rc;
+    GatePar par;
+    if (const int rc = gate_values(ctx, opts, &par)) return rc;
+    if (const int rc = sig_aligned(ctx, channels, x_dev)) return rc;
+    if (n_signals == 0) return MSG_OK;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(offsets, n, n_signals, dyn_tiles, "signal", "gate")) return rc;
+    if (c.tiles > 0 && !x_dev) return fail(ctx, MSG_E_ARG, "null input buffer");
+    // the pass writes where it reads: two signals sharing a frame would gate each other's output
+    SigRanges ranges;
+    for (int i = 0; i < n_signals; ++i)
+        if (n[i] > 0) ranges.emplace_back(offsets[i], offsets[i] + n[i]);
+    if (const int rc = sig_disjoint(ctx, ranges, "signal")) return rc;
+    if (const int rc = c.open(ctx->gate_meta)) return rc;
+    HIPCHK(ctx, ctx->gate_carry.ensure(c.parts() * 4));
+    HIPCHK(ctx, ctx->gate_trans.ensure(c.parts() * 4));
+    HIPCHK(ctx, ctx->gate_flag.ensure(c.parts()));
+    HIPCHK(ctx, ctx->gate_state.ensure((size_t)n_signals));
+    // the envelope scan runs without a tile too: it initialises the records
+    HIPCHK(ctx, launch_gate(n_signals, channels, (unsigned)c.tiles, c.s, x_dev, ctx->gate_meta.p, par, ctx->gate_carry.p,
+                            ctx->gate_trans.p, ctx->gate_flag.p, ctx->gate_state.p, rec_dev));
     return c.finish();
 }

@@ -26,6 +26,8 @@ from . import stereo as _stereo  # noqa: F401
 from .stereo import Stereo  # noqa: F401
 from . import dynamics as _dynamics  # noqa: F401
 from .dynamics import Dynamics  # noqa: F401
+from . import gate as _gate  # noqa: F401
+from .gate import Gate  # noqa: F401
 
 
 def render(params, progress=None, device: int = 0):
@@ -35,7 +37,8 @@ def render(params, progress=None, device: int = 0):
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
                  out_lufs=None, out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf",
-                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None, out_dynamics=None, out_stereo=None,
+                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None, out_gate=None, out_dynamics=None,
+                 out_stereo=None,
                  out_filter=None, out_edges=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
@@ -69,12 +72,14 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     ``channels=1``, the fold to mono in HBM, so that a mono delivery is levelled, held, reported and
     quantised as delivered and comes back as (n, 1) arrays (stereo.py; one device only).
     ``out_dynamics``: a dynamics.Dynamics, after the stereo rule and before the edges and the level
-    rules: every render compressed in HBM (dynamics.py; one device only)."""
+    rules: every render compressed in HBM (dynamics.py; one device only).  ``out_gate``: a gate.Gate,
+    after the stereo rule and before ``out_dynamics``: every render gated in HBM (gate.py; one device
+    only)."""
     if devices is not None and len(list(devices)) > 1:
         from .export import Delivery
         Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak, bits=out_bits,
                  limiter=out_limiter, report=out_report, edges=out_edges, filter=out_filter,
-                 stereo=out_stereo, dynamics=out_dynamics).one_device(
+                 stereo=out_stereo, gate=out_gate, dynamics=out_dynamics).one_device(
             "out_", len(list(devices)), companions=True)
         # an option of out_bits and no rule of one_device's: with out_bits it was refused above
         if out_shape is not None:
@@ -87,7 +92,8 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     return _rb(params_list, device, results, out_sr=out_sr, out_peak=out_peak, out_lufs=out_lufs,
                out_ceiling=out_ceiling, out_true_peak=out_true_peak, out_bits=out_bits, out_dither=out_dither,
                out_dither_seed=out_dither_seed, out_limiter=out_limiter, out_report=out_report, out_shape=out_shape,
-               out_edges=out_edges, out_filter=out_filter, out_stereo=out_stereo, out_dynamics=out_dynamics)
+               out_edges=out_edges, out_filter=out_filter, out_stereo=out_stereo, out_gate=out_gate,
+               out_dynamics=out_dynamics)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):
@@ -201,6 +207,14 @@ def dynamics(x, sr, dyn, device: int = 0):
     return _dynamics.dynamics(x, sr, dyn, device)
 
 
+def gate(x, sr, gate, device: int = 0):
+    """Gate x, (n,) or (n, 2), at sr Hz on the device with a gate.Gate: threshold, hysteresis, ratio,
+    range, linear-in-dB attack and release, hold (see gate.py).  NumPy in: a gated float32 copy and
+    its record out; a device tensor in: gated in place with no host synchronise, the device record
+    tensor out."""
+    return _gate.gate(x, sr, gate, device)
+
+
 def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0, shape=None):
     """x, (n,) or (n, 2) float32, as 16- or 24-bit PCM quantised on the device with TPDF
     dither (or "none") from the stream (seed, key); see pcm.py.  NumPy in, int16 (or
@@ -220,7 +234,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     delivered variant in a list and, with a folder, in loudness_report.csv, ``export_edges`` trimming,
     fading or looping every variant's ends, ``export_filter`` running every variant through a
     filter.Filter before them, ``export_stereo`` metering, shaping or folding to mono every variant's
-    image with a stereo.Stereo between the two, ``export_dynamics`` compressing every variant with a
-    dynamics.Dynamics after that (one device)."""
+    image with a stereo.Stereo between the two, ``export_gate`` gating every variant with a gate.Gate
+    after that and ``export_dynamics`` compressing it with a dynamics.Dynamics after that (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

@@ -139,6 +139,16 @@ class MsgDynamicsRec(C.Structure):
                 ("hold_frames", C.c_int32)]
 
 
+class MsgGateOpts(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("threshold_db", "hysteresis_db", "ratio", "range_db")] + \
+               [("attack_step", C.c_int64), ("release_step", C.c_int64), ("hold_frames", C.c_int32), ("flags", C.c_int32)]
+
+
+class MsgGateRec(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("max_e", "sum_e16", "reduced_frames", "open_frames", "opens")] + \
+               [("state", C.c_int32), ("hold_frames", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "msg_abi_version": (C.c_int, []),
@@ -221,6 +231,9 @@ _PROTOS = {
     "msg_dynamics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                                C.POINTER(MsgDynamicsOpts), C.c_void_p, C.c_void_p]),
     "msg_dynamics_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(MsgDynamicsOpts), C.c_void_p]),
+    "msg_gate_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                                 C.POINTER(MsgGateOpts), C.c_void_p, C.c_void_p]),
+    "msg_gate_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(MsgGateOpts), C.c_void_p]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),

@@ -132,8 +132,8 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
                       export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
                       export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None,
-                      export_report=None, export_shape=None, export_dynamics=None, export_stereo=None, export_filter=None,
-                      export_edges=None):
+                      export_report=None, export_shape=None, export_gate=None, export_dynamics=None, export_stereo=None,
+                      export_filter=None, export_edges=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -210,6 +210,10 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     soft knee, linear-in-dB attack, hold and release, makeup; dynamics.py), after ``export_stereo`` and
     before ``export_edges`` and the level rules, which then level, hold and report what is delivered.
     One device only.
+
+    ``export_gate``: a gate.Gate: every variant is gated in HBM (threshold, hysteresis, ratio, range,
+    linear-in-dB attack and release, hold; gate.py), after ``export_stereo`` and before
+    ``export_dynamics`` and ``export_edges``, so a trim sees the gated tail.  One device only.
     """
     from .pack import PackedBatch, out_frames
 
@@ -219,7 +223,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                         true_peak=export_true_peak, bits=export_bits, dither=export_dither,
                         dither_seed=export_dither_seed, limiter=export_limiter, report=export_report,
                         shape=export_shape, edges=export_edges, filter=export_filter, stereo=export_stereo,
-                        dynamics=export_dynamics)
+                        gate=export_gate, dynamics=export_dynamics)
     delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False,
                    rates=[merged(base_params)["base_sr"]])
     first_row = len(export_report) if export_report is not None else 0

@@ -95,8 +95,8 @@ def _out_peaks(params_list, out_peak):
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
                  out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
-                 out_limiter=None, out_report=None, out_shape=None, out_dynamics=None, out_stereo=None, out_filter=None,
-                 out_edges=None):
+                 out_limiter=None, out_report=None, out_shape=None, out_gate=None, out_dynamics=None, out_stereo=None,
+                 out_filter=None, out_edges=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -135,11 +135,14 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     quantiser work on the mono render and the arrays and tensors are (n, 1).  ``out_dynamics``: a
     dynamics.Dynamics (export.dynamics_packed), after the stereo rule and before the edges and the level
     rules: every render compressed in HBM (threshold, ratio, soft knee, linear-in-dB attack, hold and
-    release, makeup), so a report after it shows the loudness range come down."""
+    release, makeup), so a report after it shows the loudness range come down.  ``out_gate``: a gate.Gate
+    (export.gate_packed), after the stereo rule and before ``out_dynamics`` and the edges: every render
+    gated in HBM (threshold, hysteresis, ratio, range, linear-in-dB attack and release, hold), so the
+    compressor's makeup cannot lift what the gate removed and a trim sees the gated tail."""
     delivery = Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak,
                         bits=out_bits, dither=out_dither, dither_seed=out_dither_seed, limiter=out_limiter,
                         report=out_report, shape=out_shape, edges=out_edges, filter=out_filter, stereo=out_stereo,
-                        dynamics=out_dynamics)
+                        gate=out_gate, dynamics=out_dynamics)
     params_list = list(params_list)
     delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)

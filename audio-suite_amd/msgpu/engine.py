@@ -445,6 +445,20 @@ class Engine:
                           stream=stream)
         return rec
 
+    def gate_apply(self, x, offsets, lens, channels, sr, gate, stream=None):
+        """msg_gate_apply: the gate of a gate.Gate (milliseconds taken at ``sr`` Hz) over signals lying
+        in a device float32 tensor (as Engine.true_peak), in place.  Returns the device records, an
+        int64 tensor (signals, 6) whose rows are msg_gate_rec (gate.records reads them on the host);
+        enqueued on ``stream``, no host synchronise.  (Engine.gate is the stream gate between contexts.)"""
+        channels, off, cnt = self._signals(x, offsets, lens, channels)
+        opts = gate.opts(sr)
+        rec = self.torch.empty((int(off.size), 6), dtype=self.torch.int64, device=x.device)
+        if not off.size:                      # no signal: no record to point at
+            return rec
+        self._signal_call(L.lib().msg_gate_apply, x, channels, off, cnt, C.byref(opts), C.c_void_p(rec.data_ptr()),
+                          stream=stream)
+        return rec
+
     def quantize(self, x, offsets, lens, channels, bits, dither="tpdf", seed=0, keys=None, out=None, stream=None,
                  shape=None):
         """msg_quantize of signals lying in a device float32 tensor (as Engine.true_peak):

@@ -1,9 +1,9 @@
-"""The delivery chain of a rendered batch: resample -> filter -> stereo -> dynamics -> edges -> level -> report -> quantise, in HBM.
+"""The delivery chain of a rendered batch: resample -> filter -> stereo -> gate -> dynamics -> edges -> level -> report -> quantise, in HBM.
 
 ``render_batch`` (dropin.py, ``out_*`` options) and ``render_variations`` (batch.py,
 ``export_*`` options) describe what they deliver with one ``Delivery``, check it with
 ``Delivery.check`` and run it with ``deliver``; each pass works on the renders where
-they lie (resample.py, filter.py, stereo.py, dynamics.py, edges.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing
+they lie (resample.py, filter.py, stereo.py, gate.py, dynamics.py, edges.py, loudness.py, truepeak.py, limit.py, lrange.py, pcm.py) and nothing
 here synchronises, with one exception: an ``edges`` rule with a trim or a loop crossfade changes what
 is delivered of each render, so ``deliver`` reads the spans the device found (8 int64 per render)
 before it sizes the later passes.  That is the chain's one host wait; fades alone wait for nothing.
@@ -12,8 +12,8 @@ its row in ``RULES``, its lines in ``check`` and its step in ``deliver``; a pass
 renders' rates is a closure handed to ``per_rate``.  The twelve dataclass fields and their order
 are pinned by the earlier rules' tests, so ``filter``, the rule after ``edges``, is a keyword of
 ``Delivery`` and no dataclass field: ``Delivery(filter=f)``, seen by ``==`` and ``repr``; so is
-``stereo``, the rule between them in the chain, and ``dynamics``, the compressor between the stereo
-rule and the edges.  From the stereo step on a render has one channel or
+``stereo``, the rule between them in the chain, ``dynamics``, the compressor between the stereo
+rule and the edges, and ``gate``, the gate between the stereo rule and the compressor.  From the stereo step on a render has one channel or
 two: ``deliver`` carries that count through every later pass, each of which takes it as a keyword
 that defaults to 2.
 """
@@ -27,12 +27,12 @@ import numpy as np
 REPORT_DTYPE = np.dtype([(k, "<f8") for k in ("lufs", "lra", "lo", "hi", "max_momentary", "max_short", "peak",
                                               "true_peak", "dbtp")] + [("frames", "<i8"), ("rate", "<i8")])
 
-# The rules, each a field of Delivery (``filter``, ``stereo``, ``dynamics``: its keywords): (the rule, the option that comes with it, why it works on one
+# The rules, each a field of Delivery (``filter``, ``stereo``, ``dynamics``, ``gate``: its keywords): (the rule, the option that comes with it, why it works on one
 # device only, whether results "stats" may ask for it).  ``dither``, ``dither_seed`` and ``shape`` are
 # options of ``bits`` that ask for nothing alone, so they have no row.
 RULES = (("sr", "peak", " (multi.py sizes its shared memory by out_n)", False), ("lufs", "ceiling", "", False),
          ("true_peak", None, "", False), ("bits", None, "", False), ("limiter", None, "", False),
-         ("report", None, "", False), ("dynamics", None, "", False), ("stereo", None, "", False), ("edges", None, "", False),
+         ("report", None, "", False), ("gate", None, "", False), ("dynamics", None, "", False), ("stereo", None, "", False), ("edges", None, "", False),
          ("filter", None, "", False))
 
 
@@ -181,6 +181,17 @@ class DeliveryFields:
             except ValueError as e:
                 raise ValueError(f"{p}dynamics: {e}") from None
         self.one_device(p, n_devices, ("dynamics",))
+        if self.gate is not None:
+            from .gate import Gate
+            if not isinstance(self.gate, Gate):
+                raise ValueError(f"{p}gate must be None or a Gate")
+            try:
+                self.gate.check()
+                for rate in ([self.sr] if self.sr is not None else rates):
+                    self.gate.check(rate)
+            except ValueError as e:
+                raise ValueError(f"{p}gate: {e}") from None
+        self.one_device(p, n_devices, ("gate",))
         if results == "stats":
             for rule, _, _, with_stats in RULES:
                 if not with_stats and getattr(self, rule) is not None:
@@ -192,29 +203,32 @@ class Delivery(DeliveryFields):
     ``filter``, a filter.Filter whose biquad cascade runs in front of the edges and the level rules,
     and ``stereo``, a stereo.Stereo whose meter, image matrix or mono fold runs between the filter and
     the edges, and ``dynamics``, a dynamics.Dynamics whose compressor runs between the stereo rule and
-    the edges.  They are given by keyword only and are not dataclass fields (``dataclasses.fields``
+    the edges, and ``gate``, a gate.Gate whose gate runs between the stereo rule and the compressor.  They are given by keyword only and are not dataclass fields (``dataclasses.fields``
     and ``dataclasses.replace`` do not see them; ``==`` and ``repr`` do)."""
     filter = None
     stereo = None
     dynamics = None
+    gate = None
 
-    def __init__(self, *args, filter=None, stereo=None, dynamics=None, **kw):
+    def __init__(self, *args, filter=None, stereo=None, dynamics=None, gate=None, **kw):
         super().__init__(*args, **kw)
         self.filter = filter
         self.stereo = stereo
         self.dynamics = dynamics
+        self.gate = gate
 
     def __eq__(self, other):
         same = DeliveryFields.__eq__(self, other)
         if same is NotImplemented:
             return same
-        return same and self.filter == other.filter and self.stereo == other.stereo and self.dynamics == other.dynamics
+        return same and self.filter == other.filter and self.stereo == other.stereo and self.dynamics == other.dynamics \
+            and self.gate == other.gate
 
     __hash__ = None
 
     def __repr__(self):
         return DeliveryFields.__repr__(self)[:-1] + \
-            f", dynamics={self.dynamics!r}, filter={self.filter!r}, stereo={self.stereo!r})"
+            f", gate={self.gate!r}, dynamics={self.dynamics!r}, filter={self.filter!r}, stereo={self.stereo!r})"
 
     def channels(self):
         """The channels of what is delivered: 1 when the stereo rule folds to mono, else 2."""
@@ -229,7 +243,9 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     that loudness, true peak, limiter and report measure what is delivered), metered, shaped or folded
     to mono by ``delivery.stereo`` (stereo_packed: after the filter, because DC and rumble are correlation,
     and in front of the edges and the level rules, because a fold changes the level they must see; from there
-    on a render has ``delivery.channels()`` channels, (frames, 1) when folded), compressed by ``delivery.dynamics``
+    on a render has ``delivery.channels()`` channels, (frames, 1) when folded), gated by ``delivery.gate`` (gate_packed:
+    in front of the compressor, whose makeup then cannot lift what the gate removed and so that the thresholds mean the
+    rendered level, and in front of the edges, so that a trim sees the gated tail), compressed by ``delivery.dynamics``
     (dynamics_packed: the fold is compressed as delivered; in front of the edges, so that a trim sees the
     compressed level and the fades still end at zero, and in front of the level rules), its ends shaped by ``delivery.edges`` (edges_packed; from there
     on a render is the span that rule left of it), levelled at the rate delivered, metered as delivered when
@@ -249,6 +265,8 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     ch = 2
     if d.stereo is not None:
         out, offsets, ch = stereo_packed(eng, out, offsets, lens, rates, d.stereo, pending=d._pending)
+    if d.gate is not None:
+        gate_packed(eng, out, offsets, lens, rates, d.gate, channels=ch)
     if d.dynamics is not None:
         dynamics_packed(eng, out, offsets, lens, rates, d.dynamics, channels=ch)
     if d.edges is not None:
@@ -356,6 +374,16 @@ def filter_packed(eng, y, offsets, lens, rates, flt):
         eng.filter(y, off, cnt, 2, rate, flt)
         return ()
     per_rate(eng, y, offsets, lens, rates, run, ())
+
+
+def gate_packed(eng, y, offsets, lens, rates, gate, channels=2):
+    """Gate renders lying in a device tensor ((frames, ``channels``) float32, render i at frame
+    offsets[i] with lens[i] frames at rates[i] Hz) with ``gate``, a gate.Gate, where they lie:
+    msg_gate_apply per distinct rate (the milliseconds are steps and frames at the render's rate).
+    Nothing is moved.  Returns the device records in render order (engine.Engine.gate_apply); no
+    host synchronise."""
+    return per_rate(eng, y, offsets, lens, rates, lambda off, cnt, rate: eng.gate_apply(y, off, cnt, channels, rate, gate), 6,
+                    eng.torch.int64)
 
 
 def dynamics_packed(eng, y, offsets, lens, rates, dyn, channels=2):

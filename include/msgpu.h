@@ -21,6 +21,7 @@
  *   msg_quantize_shaped  the same with noise-shaped dither (error feedback)  (no counterpart)
  *   msg_limit        look-ahead true-peak limiter in HBM            (no counterpart)
  *   msg_dynamics     compressor in HBM, an exact integer envelope   (no counterpart)
+ *   msg_gate_apply   gate / expander in HBM, exact state and envelope scans  (no counterpart)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
 #ifndef MSGPU_H
@@ -638,6 +639,54 @@ int msg_dynamics(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* of
 /* The same definition as one sequential loop over one signal in host memory, in place (x: n
  * frames of `channels` interleaved words); needs no device. */
 int msg_dynamics_host(float* x, int32_t channels, int64_t n, const msg_dynamics_opts* opts, msg_dynamics_rec* rec);
+
+/* A gate (downward expander) over signals lying in HBM, in place (csrc/gate.h holds the
+ * definition, DESIGN.md 4m the kernels).  msg_gate is the stream gate between two contexts
+ * above; this pass is msg_gate_apply.  The channels are linked: p = max over the channels of |x|
+ * per frame.  Every envelope value is an int64 in [0, 2^40] in units of 2^-32 dB.  p_open is the
+ * smallest float32 at or above the level of threshold_db, p_close the same for threshold_db -
+ * hysteresis_db; the state s is 1 where p >= p_open, 0 where p < p_close and the state of the
+ * frame before otherwise, 0 in front of the signal; sh is 1 where s was 1 in one of the last
+ * hold_frames + 1 frames.  RANGE = llround(range_db 2^32), 2^40 for +inf.  The openness o is
+ * RANGE where sh = 1 and RANGE - r elsewhere, r = RANGE for ratio = +inf or p = 0 and otherwise
+ * (ratio - 1) (threshold_db - 20 log10 p) in float64 by the library's own log2, rounded to the
+ * nearest unit and clamped to [0, RANGE].  The ramps are straight lines in dB: closing
+ * F[f] = max(F[f - 1] - release_step, o[f]) runs forward from 0, opening
+ * B[f] = max(B[f + 1] - attack_step, o[f]) backward from 0 (the pass is offline: the gate is
+ * fully open where the held state opens), and E = RANGE - max(F, B).  The gain is
+ * (float) 2^(-E 2^-32 log2(10) / 20) by the library's own exp2, 0 for E = 2^40, and y = x g in
+ * float32; a frame whose gain is 1 keeps its bits.  State, hold and ramps compose exactly over
+ * integers, so the device's tiled scans and msg_gate_host's sequential loop agree to the bit,
+ * samples and records, alone or in any batch.  A signal with a NaN or an infinity anywhere is
+ * left as it was, state 2.
+ *   max_e, sum_e16     the largest E, and the sum over frames of E >> 16
+ *   reduced_frames     frames with E > 0
+ *   open_frames, opens frames with sh = 1, and those of them whose frame before has sh = 0
+ *   state              0 no frame reduced, 1 gated, 2 non-finite
+ * Steps as for msg_dynamics_opts.  Neither struct has a msg_sizeof entry. */
+typedef struct msg_gate_opts {
+    double threshold_db;       /* -150 .. 24 */
+    double hysteresis_db;      /* 0 .. 48 */
+    double ratio;              /* >= 1, +inf: closed means RANGE */
+    double range_db;           /* (0, 240], or +inf: closed frames become zero */
+    int64_t attack_step, release_step;   /* 1 .. 2^40 units per frame */
+    int32_t hold_frames;       /* 0 up */
+    int32_t flags;             /* 0 */
+} msg_gate_opts;
+typedef struct msg_gate_rec {
+    int64_t max_e, sum_e16, reduced_frames, open_frames, opens;
+    int32_t state, hold_frames;
+} msg_gate_rec;
+/* Signals as for msg_dynamics, which must not overlap.  A value of opts out of range:
+ * MSG_E_VALUE.  rec_dev: n_signals device records.  With hysteresis or a hold a read-only state
+ * sweep and its scan over tiles come first; then two sweeps over the samples and a scan over
+ * tiles between them; all enqueue back to back on stream with no host synchronise; one call in
+ * flight per context. */
+int msg_gate_apply(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* offsets, const int64_t* n,
+                   int32_t n_signals, const msg_gate_opts* opts, msg_gate_rec* rec_dev, void* stream);
+/* The same definition as one sequential loop over one signal in host memory, in place (x: n
+ * frames of `channels` interleaved words); needs no device. */
+int msg_gate_host(float* x, int32_t channels, int64_t n, const msg_gate_opts* opts, msg_gate_rec* rec);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
