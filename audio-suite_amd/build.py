@@ -34,7 +34,7 @@ OUT = os.path.join(HERE, "msgpu", "libmsgpu.so")
 TUS = ["msgpu.hip", "k_spectral.hip", "k_spectral_ct.hip", "k_spec3.hip", "k_fir.hip", "k_grain64.hip", "k_grain64_lds.hip",
        "k_grain64_glb.hip", "k_stereo_odd.hip", "k_fir64.hip", "k_stereo.hip", "k_digest.hip", "k_resample.hip",
        "k_loudness.hip", "k_truepeak.hip", "k_pcm.hip", "k_limit.hip", "k_pcm_shape.hip", "k_edges.hip", "k_filter.hip",
-       "k_image.hip", "k_dynamics.hip", "k_gate.hip"]
+       "k_image.hip", "k_dynamics.hip", "k_gate.hip", "k_flac.hip"]
 HEADERS = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
           [os.path.join(os.path.dirname(HERE), "include", "msgpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -406,6 +406,8 @@ struct msg_ctx {
     DevBuf<int64_t> gate_meta, gate_carry, gate_trans;
     DevBuf<uint32_t> gate_flag;
     DevBuf<int32_t> gate_state;
+    // msg_flac: signal extents + block bases; per block its plan (21 words) and the bytes in front of its frame
+    DevBuf<int64_t> flac_meta, flac_plan, flac_pre;
 
     // What must come first and in this order; the members' destructors follow.
     ~msg_ctx() {

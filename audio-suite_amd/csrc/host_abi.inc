@@ -3,13 +3,13 @@
 // the host references of the render digest (digest.h), of the loudness and true-peak
 // measurements (loudness.h, lrange.h, truepeak.h), of the PCM quantisers (pcm.h, pcm_shape.h) and of the look-ahead
 // limiter (limit.h), of the edges pass (edges.h), of the delivery filter (filter.h) and of the stereo
-// meter and image (image.h), of the compressor (dynamics.h) and of the gate (gate.h).  Included
+// meter and image (image.h), of the compressor (dynamics.h), of the gate (gate.h) and of the FLAC encoder (flac.h).  Included
 // inside extern "C" by msgpu.hip (the product library) and by host_san.cpp (a
 // host-only build under AddressSanitizer / UBSan, tests/test_host_sanitizers.py).
 // Needs in scope: fail(ctx, code, msg), kHostZig, the ziggurat tables, and the headers
 // named above (DigestPart / dg_host, LoudRec / ld_host, LRangeRec / lr_host, TruePeakRec / tp_host, PcmRec / pcm_host,
 // LimitRec / lim_host, EdgesRec / edg_host, FilterOpts / fl_host, ImageRec / img_meter_host / img_host,
-// DynRec / dyn_host, GateRec / gate_host).
+// DynRec / dyn_host, GateRec / gate_host, FlacRec / flac_host).
 
 int64_t msg_sizeof(int32_t which) {
     switch (which) {
@@ -409,6 +409,35 @@ int msg_debug_gate_env(float* x, int32_t channels, int64_t n, const msg_gate_opt
     if (const int rc = gate_values(nullptr, opts, &par)) return rc;
     GateRec r;
     gate_host(x, channels, n, par, &r, env, held);
+    std::memcpy(rec, &r, sizeof(r));
+    return MSG_OK;
+}
+
+// The value checks msg_flac and msg_flac_host share
+static int flac_values(msg_ctx* ctx, int32_t channels, int32_t bits, int32_t sr, int32_t block) {
+    static_assert(sizeof(FlacRec) == sizeof(msg_flac_rec) && sizeof(FlacRec) == 88, "FlacRec is msg_flac_rec");
+    if (channels != 1 && channels != 2) return fail(ctx, MSG_E_VALUE, "channels must be 1 or 2");
+    if (bits != 16 && bits != 24) return fail(ctx, MSG_E_VALUE, "bits must be 16 or 24");
+    if (!flac_rate_ok(sr)) return fail(ctx, MSG_E_VALUE, "the sample rate must be from 1 to 655350 Hz");
+    if (!flac_block_ok(block)) return fail(ctx, MSG_E_VALUE, "block must be 256, 512, 1024, 2048 or 4096");
+    return MSG_OK;
+}
+
+int64_t msg_flac_bound(int64_t frames, int32_t channels, int32_t bits, int32_t block) {
+    if (frames < 0 || frames > FLAC_MAX_FRAMES || (channels != 1 && channels != 2) || (bits != 16 && bits != 24) ||
+        !flac_block_ok(block))
+        return -1;
+    return flac_bound(frames, channels, bits, block);
+}
+
+// FLAC frames of one signal in host memory: the definition of flac.h as one sequential bit writer
+// (flac_host), the device's bytes and record to the bit
+int msg_flac_host(const void* pcm, int32_t channels, int64_t n, int32_t bits, int32_t sr, int32_t block, int32_t md5,
+                  void* out, msg_flac_rec* rec) {
+    if (!rec || n < 0 || n > FLAC_MAX_FRAMES || (n > 0 && (!pcm || !out))) return fail(nullptr, MSG_E_ARG, "bad arguments");
+    if (const int rc = flac_values(nullptr, channels, bits, sr, block)) return rc;
+    FlacRec r;
+    flac_host(static_cast<const uint8_t*>(pcm), channels, bits, n, block, sr, md5 != 0, static_cast<uint8_t*>(out), &r);
     std::memcpy(rec, &r, sizeof(r));
     return MSG_OK;
 }

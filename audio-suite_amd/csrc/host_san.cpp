@@ -6,7 +6,8 @@
 // msg_truepeak_host), of the PCM quantiser (pcm.h, msg_quantize_host) and of the
 // look-ahead limiter (limit.h, msg_limit_host), of the edges pass (edges.h, msg_edges_host) and of the
 // stereo meter and image (image.h, msg_stereo_meter_host, msg_stereo_host) and of the compressor
-// (dynamics.h, msg_dynamics_host) and of the gate (gate.h, msg_gate_host),
+// (dynamics.h, msg_dynamics_host), of the gate (gate.h, msg_gate_host) and of the FLAC encoder (flac.h,
+// msg_flac_host),
 // compiled by g++ with -fsanitize=address,undefined into
 // msgpu/libmsgpu_hostsan.so.  The device entry points are stubs that fail with
 // MSG_E_DEVICE, so the ctypes binding (_lib.py) loads this library unchanged
@@ -35,6 +36,7 @@
 #include "image.h"
 #include "dynamics.h"
 #include "gate.h"
+#include "flac.h"
 #include "../../include/msgpu.h"
 
 namespace {
@@ -136,6 +138,10 @@ int msg_dynamics(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int3
 }
 int msg_gate_apply(msg_ctx*, float*, int32_t, const int64_t*, const int64_t*, int32_t, const msg_gate_opts*, msg_gate_rec*,
                    void*) {
+    return no_device();
+}
+int msg_flac(msg_ctx*, const void*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, int32_t, int32_t, void*,
+             int64_t, msg_flac_rec*, void*) {
     return no_device();
 }
 #include "host_abi.inc"

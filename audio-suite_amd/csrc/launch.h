@@ -281,3 +281,11 @@ hipError_t launch_dynamics(int n_sig, int channels, unsigned tiles, hipStream_t 
 struct GatePar;
 hipError_t launch_gate(int n_sig, int channels, unsigned tiles, hipStream_t s, float* x, const int64_t* meta,
                        const GatePar& par, int64_t* carry, int64_t* trans, uint32_t* flag, int32_t* state, void* rec);
+
+// FLAC encoder (kernels_flac.h): the plan sweep writes every block's FlacPlan (21 words) with its
+// frame's bytes, a scan per signal turns them into the prefix pre (one word per block) and the
+// records (msg_flac_rec) but for byte_off, which a scan over the signals sets; the pack sweep writes
+// the frames into out, and with md5 a last launch hashes every signal's PCM.  meta: byte offsets,
+// frames, n_sig + 1 first blocks
+hipError_t launch_flac(int n_sig, int channels, int bits, int block, int sr, bool md5, unsigned tiles, hipStream_t s,
+                       const void* pcm, const int64_t* meta, void* plan, int64_t* pre, void* rec, void* out, int64_t out_bytes);

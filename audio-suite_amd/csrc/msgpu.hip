@@ -44,6 +44,7 @@
 #include "image.h"
 #include "dynamics.h"
 #include "gate.h"
+#include "flac.h"
 #include "host_pool.h"
 #include "er_merge.h"
 #include "batch.h"

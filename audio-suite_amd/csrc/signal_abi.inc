@@ -1,7 +1,7 @@
 // signal_abi.inc — the entry points of the C ABI (include/msgpu.h) that run one pass over
 // a ragged batch of signals lying in a device buffer: msg_digest, msg_resample,
 // msg_loudness, msg_loudness_range, msg_loudness_gain, msg_truepeak, msg_truepeak_gain, msg_quantize, msg_quantize_shaped, msg_limit,
-// msg_edges, msg_filter, msg_stereo_meter, msg_stereo, msg_dynamics, msg_gate_apply.
+// msg_edges, msg_filter, msg_stereo_meter, msg_stereo, msg_dynamics, msg_gate_apply, msg_flac.
 // Included inside extern "C" by msgpu.hip.  DESIGN.md "Signal passes".
 // Needs in scope: fail, HIPCHK, stream_handover, DoneGuard, MSG_MAX_FRAMES, ctx.h.
 //
@@ -542,5 +542,34 @@ int msg_gate_apply(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* 
     // the envelope scan runs without a tile too: it initialises the records
     HIPCHK(ctx, launch_gate(n_signals, channels, (unsigned)c.tiles, c.s, x_dev, ctx->gate_meta.p, par, ctx->gate_carry.p,
                             ctx->gate_trans.p, ctx->gate_flag.p, ctx->gate_state.p, rec_dev));
+    return c.finish();
+}
+
+int msg_flac(msg_ctx* ctx, const void* pcm_dev, int32_t channels, const int64_t* byte_off, const int64_t* n, int32_t n_signals,
+             int32_t bits, int32_t sr, int32_t block, int32_t md5, void* out_dev, int64_t out_bytes, msg_flac_rec* rec_dev,
+             void* stream) {
+    if (const int rc = sig_args(ctx, byte_off && n && rec_dev && out_bytes >= 0, n_signals, channels)) return rc;
+    if (const int rc = flac_values(ctx, channels, bits, sr, block)) return rc;
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 15) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
+        return fail(ctx, MSG_E_ARG, "the input and the output must be 16-byte aligned");
+    if (n_signals == 0) return MSG_OK;
+    SignalCall c(ctx, stream);
+    if (const int rc = c.rows(byte_off, n, n_signals, [block](int64_t f) { return flac_blocks(f, block); }, "signal", "FLAC"))
+        return rc;
+    if (c.tiles > 0 && (!pcm_dev || !out_dev)) return fail(ctx, MSG_E_ARG, "null buffer");
+    // the blocks are read as aligned words, and the output must hold every signal's worst case
+    int64_t need = 0;
+    for (int i = 0; i < n_signals; ++i) {
+        if (byte_off[i] & 15) return fail(ctx, MSG_E_VALUE, "input offsets must be multiples of 16");
+        need += (flac_bound(n[i], channels, bits, block) + 15) & ~(int64_t)15;
+    }
+    if (need > out_bytes) return fail(ctx, MSG_E_ARG, "the output is smaller than the signals' msg_flac_bound");
+    if (const int rc = c.open(ctx->flac_meta)) return rc;
+    static_assert(sizeof(FlacPlan) % 8 == 0, "plans lie in int64 words");
+    HIPCHK(ctx, ctx->flac_plan.ensure(c.parts() * (sizeof(FlacPlan) / 8)));
+    HIPCHK(ctx, ctx->flac_pre.ensure(c.parts()));
+    // the scans run without a block too: they write the records
+    HIPCHK(ctx, launch_flac(n_signals, channels, bits, block, sr, md5 != 0, (unsigned)c.tiles, c.s, pcm_dev, ctx->flac_meta.p,
+                            ctx->flac_plan.p, ctx->flac_pre.p, rec_dev, out_dev, out_bytes));
     return c.finish();
 }

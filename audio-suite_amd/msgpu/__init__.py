@@ -28,6 +28,8 @@ from . import dynamics as _dynamics  # noqa: F401
 from .dynamics import Dynamics  # noqa: F401
 from . import gate as _gate  # noqa: F401
 from .gate import Gate  # noqa: F401
+from . import flac as _flac  # noqa: F401
+from .flac import Flac  # noqa: F401
 
 
 def render(params, progress=None, device: int = 0):
@@ -37,9 +39,8 @@ def render(params, progress=None, device: int = 0):
 
 def render_batch(params_list, device: int = 0, devices=None, results: str = "audio", out_sr=None, out_peak=None,
                  out_lufs=None, out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf",
-                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None, out_gate=None, out_dynamics=None,
-                 out_stereo=None,
-                 out_filter=None, out_edges=None):
+                 out_dither_seed=0, out_limiter=None, out_report=None, out_shape=None, out_flac=None, out_gate=None,
+                 out_dynamics=None, out_stereo=None, out_filter=None, out_edges=None):
     """Render many presets; ``devices`` (e.g. range(8)) shards them across GPUs,
     one worker process per GPU (multi.py; call before this process touches the GPU).
     ``results``: "audio" ((out_n, 2) float32 arrays), "stats" (a summary per
@@ -74,12 +75,13 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
     ``out_dynamics``: a dynamics.Dynamics, after the stereo rule and before the edges and the level
     rules: every render compressed in HBM (dynamics.py; one device only).  ``out_gate``: a gate.Gate,
     after the stereo rule and before ``out_dynamics``: every render gated in HBM (gate.py; one device
-    only)."""
+    only).  ``out_flac``: a flac.Flac, with ``out_bits``: every result is the complete .flac file as a
+    uint8 array, encoded in HBM from the quantised PCM (flac.py; one device only)."""
     if devices is not None and len(list(devices)) > 1:
         from .export import Delivery
         Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak, bits=out_bits,
                  limiter=out_limiter, report=out_report, edges=out_edges, filter=out_filter,
-                 stereo=out_stereo, gate=out_gate, dynamics=out_dynamics).one_device(
+                 stereo=out_stereo, gate=out_gate, dynamics=out_dynamics, flac=out_flac).one_device(
             "out_", len(list(devices)), companions=True)
         # an option of out_bits and no rule of one_device's: with out_bits it was refused above
         if out_shape is not None:
@@ -93,7 +95,7 @@ def render_batch(params_list, device: int = 0, devices=None, results: str = "aud
                out_ceiling=out_ceiling, out_true_peak=out_true_peak, out_bits=out_bits, out_dither=out_dither,
                out_dither_seed=out_dither_seed, out_limiter=out_limiter, out_report=out_report, out_shape=out_shape,
                out_edges=out_edges, out_filter=out_filter, out_stereo=out_stereo, out_gate=out_gate,
-               out_dynamics=out_dynamics)
+               out_dynamics=out_dynamics, out_flac=out_flac)
 
 
 def DevicePool(devices, stub: bool = False, share_devices: bool = False):
@@ -215,6 +217,13 @@ def gate(x, sr, gate, device: int = 0):
     return _gate.gate(x, sr, gate, device)
 
 
+def flac(q, sr, bits, flac=None, channels=None, device: int = 0):
+    """The complete .flac file (uint8, 1-D) of integer audio q, (n,) or (n, channels), or of the packed
+    device bytes msg_quantize wrote (give ``channels``), encoded on the device with a flac.Flac
+    (block size, MD5; see flac.py): fixed predictors, Rice codes, the four stereo assignments."""
+    return _flac.encode(q, sr, bits, flac, channels, device)
+
+
 def quantize(x, bits=16, dither="tpdf", seed=0, key=0, device: int = 0, shape=None):
     """x, (n,) or (n, 2) float32, as 16- or 24-bit PCM quantised on the device with TPDF
     dither (or "none") from the stream (seed, key); see pcm.py.  NumPy in, int16 (or
@@ -235,6 +244,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     fading or looping every variant's ends, ``export_filter`` running every variant through a
     filter.Filter before them, ``export_stereo`` metering, shaping or folding to mono every variant's
     image with a stereo.Stereo between the two, ``export_gate`` gating every variant with a gate.Gate
-    after that and ``export_dynamics`` compressing it with a dynamics.Dynamics after that (one device)."""
+    after that and ``export_dynamics`` compressing it with a dynamics.Dynamics after that, ``export_flac``
+    writing FLAC files encoded on the device instead of WAVs (one device)."""
     from .batch import render_variations as _rv
     return _rv(base_params, seeds, unfolds, stretches, folder, device, devices=devices, **kw)

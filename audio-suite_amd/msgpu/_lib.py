@@ -234,6 +234,11 @@ _PROTOS = {
     "msg_gate_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                                  C.POINTER(MsgGateOpts), C.c_void_p, C.c_void_p]),
     "msg_gate_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(MsgGateOpts), C.c_void_p]),
+    "msg_flac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                           C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "msg_flac_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                C.c_void_p]),
+    "msg_flac_bound": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "msg_rng_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_int64]),
     "msg_rng_normal": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),
     "msg_rng_exponential": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.c_int64]),

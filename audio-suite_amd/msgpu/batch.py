@@ -132,8 +132,8 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                       names="wav", progress=None, devices=None, export_sr=None, export_peak=None,
                       export_lufs=None, export_ceiling=None, export_true_peak=None, export_bits=None,
                       export_dither="tpdf", export_dither_seed=0, export_records=None, export_limiter=None,
-                      export_report=None, export_shape=None, export_gate=None, export_dynamics=None, export_stereo=None,
-                      export_filter=None, export_edges=None):
+                      export_report=None, export_shape=None, export_flac_records=None, export_flac=None, export_gate=None,
+                      export_dynamics=None, export_stereo=None, export_filter=None, export_edges=None):
     """Render every (seed, unfold, stretch) variant of ``base_params`` on the device
     (or, with ``devices``, sharded across those GPUs, multi.py).
 
@@ -214,6 +214,12 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
     ``export_gate``: a gate.Gate: every variant is gated in HBM (threshold, hysteresis, ratio, range,
     linear-in-dB attack and release, hold; gate.py), after ``export_stereo`` and before
     ``export_dynamics`` and ``export_edges``, so a trim sees the gated tail.  One device only.
+
+    ``export_flac``: a flac.Flac, with ``export_bits``: the quantised PCM of every variant is encoded as
+    FLAC frames in HBM (flac.py) and only the encoded bytes cross to the host; each result's audio is the
+    complete .flac file as a uint8 array and, with a folder, ``<name>.flac`` is written instead of the
+    WAV.  ``export_records`` keeps receiving the PCM records; ``export_flac_records``: a list that gets
+    every variant's msg_flac_rec (flac.FLAC_DTYPE).  One device only.
     """
     from .pack import PackedBatch, out_frames
 
@@ -223,7 +229,7 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                         true_peak=export_true_peak, bits=export_bits, dither=export_dither,
                         dither_seed=export_dither_seed, limiter=export_limiter, report=export_report,
                         shape=export_shape, edges=export_edges, filter=export_filter, stereo=export_stereo,
-                        gate=export_gate, dynamics=export_dynamics)
+                        gate=export_gate, dynamics=export_dynamics, flac=export_flac)
     delivery.check("export_", n_devices=len(list(devices)) if devices is not None else 1, numeric_peak=False,
                    rates=[merged(base_params)["base_sr"]])
     first_row = len(export_report) if export_report is not None else 0
@@ -239,7 +245,11 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
 
     def emit(key, audio):
         name = variant_name(*key, out_sr, names)
-        if folder is not None and export_bits is not None:
+        if export_flac is not None:
+            name = name[:-4] + ".flac"                # "….wav" and the reference's "…pwav" alike
+            if folder is not None:
+                audio.tofile(os.path.join(folder, name))
+        elif folder is not None and export_bits is not None:
             write_wav_pcm(os.path.join(folder, name), audio, out_sr, export_bits)
         elif folder is not None:
             write_wav_float32(os.path.join(folder, name), audio, out_sr)
@@ -267,9 +277,15 @@ def render_variations(base_params, seeds, unfolds, stretches, folder=None, devic
                                           peaks, range(done, done + len(chunk)))
         done += len(chunk)
         eng.torch.cuda.synchronize(eng.device)
-        host = out.cpu().numpy()
+        host = (out if export_flac is None else out[:rec.total()]).cpu().numpy()
         delivery.flush_report()
-        if export_bits is not None:
+        if export_flac is not None:
+            if export_records is not None:
+                export_records.extend(records(rec.pcm))
+            if export_flac_records is not None:
+                export_flac_records.extend(rec.flac)
+            audio = rec.files(host)
+        elif export_bits is not None:
             if export_records is not None:
                 export_records.extend(records(rec))
             audio = unpack_all(host, offsets, lens, export_bits, delivery.channels())

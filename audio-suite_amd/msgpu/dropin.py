@@ -95,8 +95,8 @@ def _out_peaks(params_list, out_peak):
 
 def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=None, out_peak=None, out_lufs=None,
                  out_ceiling=None, out_true_peak=None, out_bits=None, out_dither="tpdf", out_dither_seed=0,
-                 out_limiter=None, out_report=None, out_shape=None, out_gate=None, out_dynamics=None, out_stereo=None,
-                 out_filter=None, out_edges=None):
+                 out_limiter=None, out_report=None, out_shape=None, out_flac=None, out_gate=None, out_dynamics=None,
+                 out_stereo=None, out_filter=None, out_edges=None):
     """Render many presets in one device batch; returns a list of (out_n, 2) float32
     arrays ("audio"), per-preset summaries ("stats", multi.rec_stats's fields,
     reduced on the device by msg_digest) or the device tensors themselves ("device").
@@ -138,18 +138,21 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     release, makeup), so a report after it shows the loudness range come down.  ``out_gate``: a gate.Gate
     (export.gate_packed), after the stereo rule and before ``out_dynamics`` and the edges: every render
     gated in HBM (threshold, hysteresis, ratio, range, linear-in-dB attack and release, hold), so the
-    compressor's makeup cannot lift what the gate removed and a trim sees the gated tail."""
+    compressor's makeup cannot lift what the gate removed and a trim sees the gated tail.  ``out_flac``: a
+    flac.Flac, with ``out_bits`` (export.flac_packed): the quantised PCM is encoded as FLAC frames in HBM and
+    every result is the complete .flac file as a uint8 array, stream header included ("device": the frames'
+    device bytes per render, without a header); only the encoded bytes cross to the host."""
     delivery = Delivery(sr=out_sr, peak=out_peak, lufs=out_lufs, ceiling=out_ceiling, true_peak=out_true_peak,
                         bits=out_bits, dither=out_dither, dither_seed=out_dither_seed, limiter=out_limiter,
                         report=out_report, shape=out_shape, edges=out_edges, filter=out_filter, stereo=out_stereo,
-                        gate=out_gate, dynamics=out_dynamics)
+                        gate=out_gate, dynamics=out_dynamics, flac=out_flac)
     params_list = list(params_list)
     delivery.check("out_", results, rates=[merged(p)["base_sr"] for p in params_list])
     eng = default_engine(device)
     packed = PackedBatch(params_list)
     out = eng.render_packed(packed)
     peaks = _out_peaks(params_list, out_peak) if out_sr is not None else None
-    y, off, lens, _ = deliver(eng, out, packed.offsets, packed.out_n, [merged(p)["base_sr"] for p in params_list],
+    y, off, lens, rec = deliver(eng, out, packed.offsets, packed.out_n, [merged(p)["base_sr"] for p in params_list],
                               delivery, peaks, range(len(params_list)))
     if results == "device":
         delivery.flush_report()
@@ -159,6 +162,8 @@ def render_batch(params_list, device: int = 0, results: str = "audio", out_sr=No
     if results == "stats":
         from .multi import device_stats
         return device_stats(eng, out, packed.offsets, packed.out_n)
+    if out_flac is not None:                     # the encoded bytes cross and nothing more
+        return rec.files(y[:rec.total()].cpu().numpy())
     host = y.cpu().numpy()                       # quantised: the bytes cross, not the float32 renders
     if out_bits is not None:
         return unpack_all(host, off, lens, out_bits, delivery.channels())

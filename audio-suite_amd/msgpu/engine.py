@@ -503,6 +503,48 @@ class Engine:
             self._signal_call(L.lib().msg_quantize_shaped, x, channels, off, cnt, bits, code, scode, *tail, stream=stream)
         return out, byte_off, rec
 
+    def flac(self, pcm, byte_offsets, lens, channels, bits, sr, block=4096, md5=True, out=None, stream=None):
+        """msg_flac: the FLAC frames of signals lying as packed PCM in a device uint8 tensor, as
+        Engine.quantize left them (signal i at byte_offsets[i], a multiple of 16, with lens[i]
+        frames of ``channels`` words of ``bits`` bits).  Returns ``(out, rec)``: a uint8 device
+        tensor sized for the worst case (``out``: a tensor to write into instead of a new one) in
+        which signal i's frames lie at rec[i].byte_off, compact across the batch, and the device
+        records, an int64 tensor (signals, 11) whose rows are msg_flac_rec (flac.records reads them on
+        the host).  Enqueued on ``stream``, no host synchronise."""
+        from .flac import BLOCKS, REC_WORDS, check_rate
+        from .pcm import check_bits
+        torch = self.torch
+        if pcm.dtype != torch.uint8 or not pcm.is_contiguous() or pcm.device.type != "cuda" or pcm.data_ptr() % 16:
+            raise ValueError("pcm must be a contiguous 16-byte aligned uint8 device tensor")
+        channels, bits, sr = int(channels), check_bits(bits), check_rate(sr)
+        if channels not in (1, 2):
+            raise ValueError("channels must be 1 or 2")
+        if isinstance(block, bool) or block not in BLOCKS:
+            raise ValueError("block must be 256, 512, 1024, 2048 or 4096")
+        off = np.ascontiguousarray(byte_offsets, dtype=np.int64)
+        cnt = np.ascontiguousarray(lens, dtype=np.int64)
+        if off.shape != cnt.shape or off.ndim != 1:
+            raise ValueError("byte_offsets and lens must be 1-D of one length")
+        n = int(off.size)
+        frame = channels * (bits // 8)
+        if n and (int(off.min()) < 0 or int(cnt.min()) < 0 or int((off + cnt * frame).max()) > pcm.numel()):
+            raise ValueError("a signal extends past the pcm tensor")
+        if n and int((off & 15).max()):
+            raise ValueError("byte_offsets must be multiples of 16")
+        lib = L.lib()
+        need = sum((int(lib.msg_flac_bound(int(c), channels, bits, int(block))) + 15) // 16 * 16 for c in cnt)
+        if out is None:
+            out = torch.empty(need, dtype=torch.uint8, device=pcm.device)
+        elif (out.dtype != torch.uint8 or not out.is_contiguous() or out.device != pcm.device or out.numel() < need or
+              out.data_ptr() % 16):
+            raise ValueError("out must be a contiguous 16-byte aligned uint8 tensor on pcm's device, large enough")
+        rec = torch.empty((n, REC_WORDS), dtype=torch.int64, device=pcm.device)
+        if not n:                             # no signal: no record to point at
+            return out, rec
+        self._signal_call(lib.msg_flac, pcm, channels, off, cnt, bits, sr, int(block), int(bool(md5)),
+                          C.c_void_p(out.data_ptr()), int(out.numel()), C.c_void_p(rec.data_ptr()), stream=stream)
+        return out, rec
+
     # ---- last-batch inspection -----------------------------------------
     def last_plan(self):
         arr = (L.MsgPlanInfo * self._last_n)()

@@ -1,4 +1,4 @@
-"""The delivery chain of a rendered batch: resample -> filter -> stereo -> gate -> dynamics -> edges -> level -> report -> quantise, in HBM.
+"""The delivery chain of a rendered batch: resample -> filter -> stereo -> gate -> dynamics -> edges -> level -> report -> quantise -> FLAC, in HBM.
 
 ``render_batch`` (dropin.py, ``out_*`` options) and ``render_variations`` (batch.py,
 ``export_*`` options) describe what they deliver with one ``Delivery``, check it with
@@ -7,13 +7,16 @@ they lie (resample.py, filter.py, stereo.py, gate.py, dynamics.py, edges.py, lou
 here synchronises, with one exception: an ``edges`` rule with a trim or a loop crossfade changes what
 is delivered of each render, so ``deliver`` reads the spans the device found (8 int64 per render)
 before it sizes the later passes.  That is the chain's one host wait; fades alone wait for nothing.
+A ``flac`` rule is the second: the encoded lengths are only known on the device, so ``deliver`` reads
+the FLAC records (11 int64 per render) and the front end then copies exactly the encoded bytes.
 A new export rule is a field of ``Delivery`` (after the last one, so the positional order stays),
 its row in ``RULES``, its lines in ``check`` and its step in ``deliver``; a pass that runs at the
 renders' rates is a closure handed to ``per_rate``.  The twelve dataclass fields and their order
 are pinned by the earlier rules' tests, so ``filter``, the rule after ``edges``, is a keyword of
 ``Delivery`` and no dataclass field: ``Delivery(filter=f)``, seen by ``==`` and ``repr``; so is
 ``stereo``, the rule between them in the chain, ``dynamics``, the compressor between the stereo
-rule and the edges, and ``gate``, the gate between the stereo rule and the compressor.  From the stereo step on a render has one channel or
+rule and the edges, ``gate``, the gate between the stereo rule and the compressor, and ``flac``, the
+FLAC encoder after the quantiser.  From the stereo step on a render has one channel or
 two: ``deliver`` carries that count through every later pass, each of which takes it as a keyword
 that defaults to 2.
 """
@@ -27,12 +30,12 @@ import numpy as np
 REPORT_DTYPE = np.dtype([(k, "<f8") for k in ("lufs", "lra", "lo", "hi", "max_momentary", "max_short", "peak",
                                               "true_peak", "dbtp")] + [("frames", "<i8"), ("rate", "<i8")])
 
-# The rules, each a field of Delivery (``filter``, ``stereo``, ``dynamics``, ``gate``: its keywords): (the rule, the option that comes with it, why it works on one
+# The rules, each a field of Delivery (``filter``, ``stereo``, ``dynamics``, ``gate``, ``flac``: its keywords): (the rule, the option that comes with it, why it works on one
 # device only, whether results "stats" may ask for it).  ``dither``, ``dither_seed`` and ``shape`` are
 # options of ``bits`` that ask for nothing alone, so they have no row.
 RULES = (("sr", "peak", " (multi.py sizes its shared memory by out_n)", False), ("lufs", "ceiling", "", False),
          ("true_peak", None, "", False), ("bits", None, "", False), ("limiter", None, "", False),
-         ("report", None, "", False), ("gate", None, "", False), ("dynamics", None, "", False), ("stereo", None, "", False), ("edges", None, "", False),
+         ("report", None, "", False), ("flac", None, "", False), ("gate", None, "", False), ("dynamics", None, "", False), ("stereo", None, "", False), ("edges", None, "", False),
          ("filter", None, "", False))
 
 
@@ -192,6 +195,19 @@ class DeliveryFields:
             except ValueError as e:
                 raise ValueError(f"{p}gate: {e}") from None
         self.one_device(p, n_devices, ("gate",))
+        if self.flac is not None:
+            from .flac import Flac
+            if not isinstance(self.flac, Flac):
+                raise ValueError(f"{p}flac must be None or a Flac")
+            if self.bits is None:
+                raise ValueError(f"{p}flac needs {p}bits")
+            try:
+                self.flac.check()
+                for rate in ([self.sr] if self.sr is not None else rates):
+                    self.flac.check(rate)
+            except ValueError as e:
+                raise ValueError(f"{p}flac: {e}") from None
+        self.one_device(p, n_devices, ("flac",))
         if results == "stats":
             for rule, _, _, with_stats in RULES:
                 if not with_stats and getattr(self, rule) is not None:
@@ -203,32 +219,35 @@ class Delivery(DeliveryFields):
     ``filter``, a filter.Filter whose biquad cascade runs in front of the edges and the level rules,
     and ``stereo``, a stereo.Stereo whose meter, image matrix or mono fold runs between the filter and
     the edges, and ``dynamics``, a dynamics.Dynamics whose compressor runs between the stereo rule and
-    the edges, and ``gate``, a gate.Gate whose gate runs between the stereo rule and the compressor.  They are given by keyword only and are not dataclass fields (``dataclasses.fields``
+    the edges, and ``gate``, a gate.Gate whose gate runs between the stereo rule and the compressor, and ``flac``, a
+    flac.Flac that encodes what the quantiser packed as FLAC frames.  They are given by keyword only and are not dataclass fields (``dataclasses.fields``
     and ``dataclasses.replace`` do not see them; ``==`` and ``repr`` do)."""
     filter = None
     stereo = None
     dynamics = None
     gate = None
+    flac = None
 
-    def __init__(self, *args, filter=None, stereo=None, dynamics=None, gate=None, **kw):
+    def __init__(self, *args, filter=None, stereo=None, dynamics=None, gate=None, flac=None, **kw):
         super().__init__(*args, **kw)
         self.filter = filter
         self.stereo = stereo
         self.dynamics = dynamics
         self.gate = gate
+        self.flac = flac
 
     def __eq__(self, other):
         same = DeliveryFields.__eq__(self, other)
         if same is NotImplemented:
             return same
         return same and self.filter == other.filter and self.stereo == other.stereo and self.dynamics == other.dynamics \
-            and self.gate == other.gate
+            and self.gate == other.gate and self.flac == other.flac
 
     __hash__ = None
 
     def __repr__(self):
         return DeliveryFields.__repr__(self)[:-1] + \
-            f", gate={self.gate!r}, dynamics={self.dynamics!r}, filter={self.filter!r}, stereo={self.stereo!r})"
+            f", flac={self.flac!r}, gate={self.gate!r}, dynamics={self.dynamics!r}, filter={self.filter!r}, stereo={self.stereo!r})"
 
     def channels(self):
         """The channels of what is delivered: 1 when the stereo rule folds to mono, else 2."""
@@ -255,7 +274,10 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
     rec): the float32 renders with frame offsets and lengths and None, or, quantised, the
     packed bytes with byte offsets and lengths and the device PCM records.  Enqueued on
     the current stream; no host synchronise, but for the spans of an ``edges`` rule that trims or
-    loops (the module's docstring)."""
+    loops (the module's docstring).  With ``delivery.flac`` the packed bytes are encoded where they lie
+    (flac_packed) and what comes back is the frames' bytes, each render's byte offset and byte count in
+    them as the device's records give them, and a FlacDelivery with the PCM records (device) and the
+    FLAC records (host): reading those is the chain's second host wait."""
     d = delivery
     if d.sr is not None:
         out, offsets, lens = resample_packed(eng, out, offsets, lens, rates, int(d.sr), peaks)
@@ -276,7 +298,11 @@ def deliver(eng, out, offsets, lens, rates, delivery, peaks=None, keys=None):
         d._pending.append(report_packed(eng, out, offsets, lens, rates, channels=ch))
     if d.bits is None:
         return out, offsets, lens, None
-    return quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys, d.shape, channels=ch)
+    q = quantize_packed(eng, out, offsets, lens, d.bits, d.dither, d.dither_seed, keys, d.shape, channels=ch)
+    if d.flac is None:
+        return q
+    frames, rec = flac_packed(eng, q[0], q[1], lens, rates, d.flac, d.bits, channels=ch)
+    return frames, rec["byte_off"].copy(), rec["bytes"].copy(), FlacDelivery(q[3], rec, rates, ch, d.bits, d.flac.block)
 
 
 def _extents(offsets, lens, rates):
@@ -561,6 +587,51 @@ def quantize_packed(eng, y, offsets, lens, bits, dither="tpdf", seed=0, keys=Non
     lens = np.asarray(lens, dtype=np.int64)
     out, byte_off, rec = eng.quantize(y, offsets, lens, channels, bits, dither, seed, keys, shape=shape)
     return out, byte_off, lens * (int(channels) * (int(bits) // 8)), rec
+
+
+class FlacDelivery:
+    """What ``deliver`` hands back with a ``flac`` rule: ``pcm``, the quantiser's device records, and
+    ``flac``, the encoder's records on the host (flac.FLAC_DTYPE, ``byte_off`` in the delivered buffer);
+    ``files`` cuts the complete .flac files out of the delivered bytes once they are on the host."""
+
+    def __init__(self, pcm, flac, rates, channels, bits, block):
+        self.pcm, self.flac, self.rates, self.channels, self.bits, self.block = pcm, flac, rates, channels, bits, block
+
+    def total(self):
+        from .flac import total_bytes
+        return total_bytes(self.flac)
+
+    def files(self, host):
+        from .flac import files
+        return [files(host, self.flac[i:i + 1], self.rates[i], self.channels, self.bits, self.block)[0]
+                for i in range(len(self.flac))]
+
+
+def flac_packed(eng, pcm, byte_off, lens, rates, flac, bits, channels=2):
+    """The packed PCM quantize_packed left in a device byte tensor (render i at byte_off[i] with lens[i]
+    frames of ``channels`` words at rates[i] Hz) as FLAC frames, encoded where it lies: msg_flac per
+    distinct rate (the rate is in every frame header) into one output tensor.  Returns (the frames'
+    bytes, the records on the host in render order, ``byte_off`` counted in that tensor): reading the
+    records waits for the device, because only they know the encoded lengths.  One rate: the output is
+    compact, byte_off the 16-byte-rounded prefix of the lengths."""
+    from .flac import FLAC_DTYPE, bound, records
+    byte_off, lens, rates = _extents(byte_off, lens, rates)
+    groups = rate_groups(rates)
+    need = [sum((bound(lens[i], channels, bits, flac.block) + 15) // 16 * 16 for i in idx) for _, idx in groups]
+    out = eng.torch.empty(int(sum(need)), dtype=eng.torch.uint8, device=pcm.device)
+    rec = np.zeros(len(rates), dtype=FLAC_DTYPE)
+    got, base = [], 0
+    for (rate, idx), size in zip(groups, need):
+        got.append(eng.flac(pcm, byte_off[idx], lens[idx], channels, bits, rate, flac.block, flac.md5,
+                            out=out[base:base + size])[1])
+        base += size
+    base = 0
+    for (rate, idx), size, r in zip(groups, need, got):
+        r = records(r)
+        r["byte_off"] += base
+        rec[idx] = r
+        base += size
+    return out, rec
 
 
 def unpack_all(host, byte_off, nbytes, bits, channels=2):

@@ -22,6 +22,7 @@
  *   msg_limit        look-ahead true-peak limiter in HBM            (no counterpart)
  *   msg_dynamics     compressor in HBM, an exact integer envelope   (no counterpart)
  *   msg_gate_apply   gate / expander in HBM, exact state and envelope scans  (no counterpart)
+ *   msg_flac         FLAC frames from the quantised PCM in HBM, fixed predictors  (no counterpart)
  *   msg_rng_*        NumPy PCG64 stream primitives, host-side   (np.random.default_rng)
  */
 #ifndef MSGPU_H
@@ -687,6 +688,43 @@ int msg_gate_apply(msg_ctx* ctx, float* x_dev, int32_t channels, const int64_t* 
 /* The same definition as one sequential loop over one signal in host memory, in place (x: n
  * frames of `channels` interleaved words); needs no device. */
 int msg_gate_host(float* x, int32_t channels, int64_t n, const msg_gate_opts* opts, msg_gate_rec* rec);
+
+/* FLAC delivery: what msg_quantize / msg_quantize_shaped left in HBM (packed little-endian PCM,
+ * bits 16 or 24, channels 1 or 2, signal i at byte_off[i], a multiple of 16, with n[i] frames)
+ * as the FLAC frames of each signal, back to back (csrc/flac.h holds the definition, DESIGN.md 4n
+ * the kernels).  Fixed predictors of order 0 .. 4, partitioned Rice codes, constant and verbatim
+ * subframes, the four stereo assignments; block: 256, 512, 1024, 2048 or 4096 frames per block.
+ * Everything is integer: the device's frames and records are msg_flac_host's sequential bit
+ * writer's, alone or in any batch.  The 42-byte stream header is the caller's, from the record.
+ *   byte_off, bytes    where the signal's frames lie in out, and how many bytes they are
+ *   frames, samples    FLAC frames (blocks), and the signal's frames per channel
+ *   min_frame, max_frame   the smallest and largest FLAC frame in bytes (0 without one)
+ *   md5                of the signal's packed PCM bytes; flags bit 0 says it was computed
+ *   constant, verbatim, fixed   subframes of each kind
+ *   assign             stereo frames coded as L+R, L+side, side+R, mid+side */
+typedef struct msg_flac_rec {
+    int64_t byte_off, bytes, frames, samples;
+    int32_t min_frame, max_frame;
+    uint8_t md5[16];
+    int32_t constant, verbatim, fixed, flags;
+    int32_t assign[4];
+} msg_flac_rec;
+/* The most bytes the frames of one signal can take: per block of m frames
+ * 16 + channels (1 + m bits / 8) + 2.  -1 for a value out of range. */
+int64_t msg_flac_bound(int64_t frames, int32_t channels, int32_t bits, int32_t block);
+/* out_dev: out_bytes bytes, 16-byte aligned, at least the sum over the signals of msg_flac_bound
+ * rounded up to 16.  Signal i's frames land at rec[i].byte_off, the prefix of the signals' byte
+ * counts each rounded up to 16, so the output is compact; the lengths are known on the device
+ * only.  sr outside 1 .. 655350, bits, block or channels out of range: MSG_E_VALUE.  A plan sweep,
+ * two scans, a pack sweep and, with md5 != 0, the MD5 launch enqueue back to back on stream with
+ * no host synchronise; one call in flight per context. */
+int msg_flac(msg_ctx* ctx, const void* pcm_dev, int32_t channels, const int64_t* byte_off, const int64_t* n,
+             int32_t n_signals, int32_t bits, int32_t sr, int32_t block, int32_t md5, void* out_dev, int64_t out_bytes,
+             msg_flac_rec* rec_dev, void* stream);
+/* The same definition as one sequential bit writer over one signal in host memory; out has room
+ * for msg_flac_bound bytes; rec->byte_off is 0.  Needs no device. */
+int msg_flac_host(const void* pcm, int32_t channels, int64_t n, int32_t bits, int32_t sr, int32_t block, int32_t md5,
+                  void* out, msg_flac_rec* rec);
 
 /* ---- NumPy stream primitives on the host (tests pin them against NumPy) ---- */
 /* Raw PCG64 outputs of np.random.default_rng(seed).bit_generator.random_raw(n). */
